@@ -18,8 +18,8 @@ so no step replays the previous step's input on its lane (the K1 capacity and K9
 segment-count guesses from the previous run are exercised inside the timed region).
   --frames F     weak scaling instead: F frames per GPU (F=100 is configs[2], round 1's line)
   --dense        configs[4]'s density (~500k points per frame, rpt.synth.dense_config)
-  --h2d-steps K  also time K steps that first copy the echo from pinned host memory (reported
-                 as `h2d_inclusive`, never as `value`)
+  --h2d-steps K  with --full: also time K steps that first copy the echo from pinned host memory
+                 (reported as `h2d_inclusive`, never as `value`)
 100 timed steps by default: with stacks in flight the timed region holds the pipeline's fill and
 drain (about one stack time per lane in flight), so short runs report less (1000 frames, same box:
 6.12 Gpoints/s at 20 steps, 6.47 at 40, 6.9 at 100); `steady_state` gives the rate without them.
@@ -29,8 +29,8 @@ latency-bound kernels share the CUs; interleaved same-box runs with every lane s
 2 lanes 8.4 ms per step, 3 lanes 7.9-8.3, 4 lanes 8.1, 5 lanes 7.95, 6 lanes 7.9-8.2; 100 steps:
 3 lanes 7.34-7.67, 5 lanes 7.35-7.43, steady state 7.06-7.38 against 6.77-6.92).  Every lane runs
 one untimed stack before the warm-up steps (its buffers are allocated on first use: a lane left
-cold cost ~80 ms inside the timed region); `one_stack_in_flight` repeats the steps strictly one after
-another, and K5's roofline is taken from that leg (K5 alone on the GPU).
+cold cost ~80 ms inside the timed region); with --full `one_stack_in_flight` repeats the steps
+strictly one after another, and K5's roofline is taken from that leg (K5 alone on the GPU).
 At N>1 (the frame-sharded path) four stacks are in flight per rank by default, their
 collectives through ONE communicator in a fixed software-pipeline order (rpt.dist.CommSequencer
 with NativeShardPipeline.SLOT_OFFSETS: every rank issues the same collectives in the same order;
@@ -42,17 +42,30 @@ process group has a finite timeout (RPT_PG_TIMEOUT_S, default 240 s) and a hang 
 (RPT_HANG_S, default 180 s without a step submitted or finished) dumps every thread's Python
 stack -- the lane threads name the collective slot they wait in -- and exits non-zero, so a
 cross-GPU ordering fault ends the run instead of hanging it.
-After the timed region (N=1, timing on), K5 is also timed on the per-GPU shares at 8 GPUs, where
+With --full (N=1, timing on), K5 is also timed on the per-GPU shares at 8 GPUs, where
 SURVEY.md §8(d) sets the 0.40 roofline target: `roofline_c4_share` (125 standard frames, the
 configs[3] stack's share) and `roofline_configs4_share` (125 dense frames, configs[4]'s), one
 stack in flight (`--no-dense-k5` skips both).
-`cpu_baseline`: oracle/refpath.py -- the reference's own algorithmic structure (whole-stack
+`cpu_baseline` (--full): oracle/refpath.py -- the reference's own algorithmic structure (whole-stack
 sklearn BallTree, per-neighbour time filter, seed-set expansion; calibrated against the
 reference in the build container by tools/time_reference.py --calibrate-refpath,
 profiles/r4/refpath_calibration.json) -- on the first frame
 of the same stack, one thread, on this node's host.
 
+A plain run does only what the headline figure needs: set-up, the lanes' untimed first stacks, the
+warm-up steps, the `--steps` timed steps, the result line (value, ms_per_step, steady_state, the
+stage times and the roofline figures of the timed steps themselves).  Every leg that takes runs of
+its own -- `one_stack_in_flight` (and the K5 roofline / stage times taken from it),
+`h2d_inclusive`, `roofline_c4_share` / `roofline_configs4_share` and `cpu_baseline` -- runs only
+with `--full`; there the `--no-*` switches and `--h2d-steps 0` still drop single legs.
+  --full              also run the legs above (their fields are null in a plain run)
+  --dump-outputs DIR  after the timed steps, write what the last timed step handed back (counts,
+                      per-segment summaries, cluster order, tracked objects) as DIR/<name>.npy
+                      (float32 / float64): with the same arguments the stacks are the same from
+                      run to run, so two builds can be compared output for output
+
     python bench.py [--gpus N] [--steps K] [--warmup W] [--total-frames T | --frames F] [--dense]
+                    [--full] [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -277,6 +290,67 @@ def _k5_share(dev, cfg, label, wkey):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(res, out_dir, dist: bool):
+    """Writes what a caller of the timed path received from one step (a StackResult, or rank 0's
+    ShardResult) as out_dir/<name>.npy: integers as float64 (exact below 2^53), floats in their
+    own width.  An array that would take the total past DUMP_MAX_BYTES is cut to a fixed seeded
+    sample of its rows (sorted indices, generator seed 0), the same from run to run.
+    counts.npy holds the scalars in the order of `counts` below; objects.npy one row per tracked
+    object (id, type, last seen frame, positions, velocities, average velocity, colour)."""
+    out = {}
+    if dist:
+        counts = {"n_points": res.n_points_global, "n_clustered_input": res.n_clustered_local,
+                  "n_clusters": res.n_clusters, "n_segments": res.n_segments}
+        frame_ids = res.built_global
+        if res.labels_local is not None:
+            out["labels_local"] = res.labels_local.cpu().numpy()
+    else:
+        counts = {"n_points": res.n_points, "n_clustered_input": res.n_clustered_input,
+                  "n_land_cells": res.n_land_cells, "n_clusters": res.n_clusters,
+                  "n_segments": res.n_segments}
+        frame_ids = res.frame_ids
+        out["first_noise"] = res.first_noise
+    out["frame_ids"] = frame_ids
+    for k, v in (res.seg or {}).items():
+        out[f"seg_{k}"] = v
+    out["frame_order_offsets"] = res.frame_order_offsets
+    out["frame_order"] = res.frame_order
+    if res.tracker is not None:
+        objs = res.tracker.objects()
+        counts["n_objects"] = len(objs)
+        types = ("unknown", "buoy", "boat")
+        out["objects"] = np.array(
+            [[o.object_id, types.index(o.object_type), o.last_seen_frame, len(o.positions),
+              len(o.velocities), float(o.average_velocity), *o.color] for o in objs],
+            dtype=np.float64).reshape(len(objs), 9)
+        out["object_positions"] = np.array(
+            [[o.object_id, f, p[0], p[1]] for o in objs for f, p in zip(o.frames_seen, o.positions)],
+            dtype=np.float64).reshape(-1, 4)
+        out["object_velocities"] = np.array(
+            [[o.object_id, v[0], v[1]] for o in objs for v in o.velocities],
+            dtype=np.float64).reshape(-1, 3)
+    out["counts"] = np.array(list(counts.values()), dtype=np.float64)
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {}
+    for name, a in out.items():
+        if a is None:
+            continue
+        a = np.asarray(a)
+        arrays[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+    budget = DUMP_MAX_BYTES - 4096 * len(arrays)  # .npy headers
+    share = budget // max(len(arrays), 1)
+    for name, a in arrays.items():
+        if a.nbytes > share:
+            rows = max(int(share // max(a.nbytes // len(a), 1)), 1)
+            idx = np.sort(np.random.default_rng(0).choice(len(a), size=rows, replace=False))
+            a = a[idx]
+        np.save(out_dir / f"{name}.npy", a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -287,6 +361,12 @@ def main():
     ap.add_argument("--frames", type=int, default=None,
                     help="frames per GPU instead (weak scaling)")
     ap.add_argument("--dense", action="store_true", help="configs[4] density (~500k pts/frame)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: "
+                         "one stack in flight, H2D-inclusive steps, K5 at the 8-GPU shares, the "
+                         "CPU baselines (a plain run leaves their fields null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step handed back as DIR/<name>.npy")
     ap.add_argument("--single-seed", action="store_true",
                     help="replay ONE stack every step (round-2 behaviour) instead of alternating "
                          "two differently seeded stacks")
@@ -329,8 +409,10 @@ def main():
                     help="run each step's host stage (order + tracker) inline instead of "
                          "overlapping it with the next step's device work")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
-    world = int(os.environ.get("WORLD_SIZE", "1"))
+    world =int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     if args.lanes is None:
         # N > 1: four stacks in flight per rank, their collectives through ONE communicator in
@@ -515,6 +597,8 @@ def main():
     summary["points_per_stack"] = sorted({int(points_of(r)) for r in results})
     value = pts_total / dt / 1e6
     ms_step = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(res, args.dump_outputs, dist)
     # steady state: the steps after the pipeline has filled (the first `lanes` steps) up to the
     # last step's device completion (the last host stage -- the drain -- excluded); max over ranks
     steady = None
@@ -541,7 +625,7 @@ def main():
     # is taken here, where its kernels have the GPU to themselves (with several stacks in flight
     # the other stacks' kernels share the CUs and stretch every event-timed stage)
     seq = None
-    if sharded_lanes:  # every rank: lane 0's pipeline, one stack at a time
+    if sharded_lanes and args.full:  # every rank: lane 0's pipeline, one stack at a time
         for k in range(max(args.warmup, 1)):
             ops.run(echoes[k % E], rank * F).finish()
         torch.cuda.synchronize(dev)
@@ -568,7 +652,7 @@ def main():
             for r in sres:
                 for key, v in r.stage_ms.items():
                     stage_acc[key] = stage_acc.get(key, 0.0) + v
-    if not dist and args.lanes > 1 and not args.no_one_stack:
+    if args.full and not dist and args.lanes > 1 and not args.no_one_stack:
         spipe = FrameStackPipeline(cfg.gains, cfg.rows, cfg.bins, PathParams(), dev, timing=timing,
                                    async_host=not args.sync_host, lanes=1)
         spipe.set_geometry(np.full(cfg.rows, cfg.scale, np.float32), ds.geo.cos_t,
@@ -597,7 +681,7 @@ def main():
 
     # optional leg: steps with the echo's H2D copy from pinned host memory inside (stack 0)
     h2d = None
-    if args.h2d_steps > 0:
+    if args.full and args.h2d_steps > 0:
         echo = echoes[0]
         host = torch.empty(echo.shape, dtype=echo.dtype, pin_memory=True)
         host.copy_(echo)
@@ -667,7 +751,8 @@ def main():
     # K5 again at the per-GPU shares where SURVEY 8(d) sets its 0.40 target (8 GPUs): the
     # configs[3] stack's 125 standard frames and configs[4]'s 125 dense frames
     roof_c4 = roof_c4d = None
-    if rank == 0 and not dist and not args.dense and timing and not args.no_dense_k5:
+    if args.full and rank == 0 and not dist and not args.dense and timing \
+            and not args.no_dense_k5:
         from rpt.synth import dense_config
 
         roof_c4 = _k5_share(dev, SynthConfig(n_frames=125),
@@ -678,7 +763,7 @@ def main():
                              "(~490k pts/frame)", "dense_125f")
 
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline and not dist:
+    if args.full and rank == 0 and not args.no_cpu_baseline and not dist:
         cf = min(args.cpu_frames, F)
         eh = echoes[0][:cf].cpu().numpy()
         npts, nfr, cdt, same, index = cpu_baseline(eh, cfg, ds.geo, structure=True)

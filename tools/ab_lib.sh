@@ -13,7 +13,7 @@ fi
 FR=${FR:-1000}
 run() {  # tag env...
   local tag=$1; shift
-  env "$@" timeout -k 10 240 python bench.py --total-frames $FR --steps 20 --warmup 3 \
+  env "$@" timeout -k 10 240 python bench.py --full --total-frames $FR --steps 20 --warmup 3 \
     --no-cpu-baseline --h2d-steps 0 > gpurun_out/ab_$tag.json 2> gpurun_out/ab_$tag.err || return 1
   python - "$tag" <<'PY'
 import json, sys

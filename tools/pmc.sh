@@ -9,7 +9,7 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp
 for C in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 600 rocprofv3 --pmc $C --output-format csv -d "$R/gpurun_out/pmc_$C" -o pmc \
-    -- python "$R/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-timing \
+    -- python "$R/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline --no-timing \
     > "gpurun_out/pmc_$C.log" 2>&1
   rc=$?; echo "pmc $C rc=$rc" >> "gpurun_out/pmc_$C.log"; [ $rc -eq 0 ] || exit $rc
 done

@@ -5,7 +5,7 @@
 set -e
 O=gpurun_out/rccl_ab
 mkdir -p $O
-B="python bench.py --sharded --total-frames 125 --steps 40 --warmup 6 --no-cpu-baseline --h2d-steps 0"
+B="python bench.py --full --sharded --total-frames 125 --steps 40 --warmup 6 --no-cpu-baseline --h2d-steps 0"
 for rep in 1 2; do
   for lanes in 1 3; do
     timeout -k 10 150 $B --lanes $lanes > $O/id_l${lanes}_r${rep}.json 2> $O/id_l${lanes}_r${rep}.err
