@@ -480,6 +480,16 @@ static int label_core_orig() {
   return v;
 }
 
+// RPT_CELL_COMP=0: the per-point union init / component / core-label kernels also on grids whose
+// cells are all mutual (k_parent_init_cells, k_cell_comp, k_label_core_cells otherwise)
+static bool cell_comp_enabled() {
+  static const bool on = [] {
+    const char* e = ab_env("RPT_CELL_COMP");
+    return !(e && std::atoi(e) == 0);
+  }();
+  return on;
+}
+
 // RPT_CHUNK_SCAN=1: the one-block-per-slab k_slab_chunk_scan (A/B)
 static bool chunk_scan_legacy() {
   static const bool v = [] {
@@ -2478,6 +2488,39 @@ __global__ __launch_bounds__(kBlock) void k_parent_init_pair(
   }
 }
 
+// The star initialisation per CELL, for grids on which every occupied cell is mutual
+// (DbscanState::all_mutual): a cell's core points are one component, so the union passes and the
+// per-cell component pass (k_cell_comp) only ever read parent[] of cell representatives -- the
+// other points' entries are not written at all.  One thread per occupied cell: rep[c] = the
+// sorted index of the cell's minimum-original-index core point (-1: no core point), which is
+// its own root.  Folded in: the union passes' list counters (as k_init_occ_cells), and the label
+// stage's clears that k_cell_roots carries on the generic path (minimum bits, cell_key = INT_MAX
+// for all cells; both first written by k_cell_comp).
+__global__ __launch_bounds__(kBlock) void k_parent_init_cells(
+    const int32_t* __restrict__ occ, const int32_t* __restrict__ n_occ, int64_t cells,
+    const unsigned long long* __restrict__ cmin, int32_t* __restrict__ rep,
+    int32_t* __restrict__ parent, int32_t* __restrict__ zero_counter,
+    int32_t* __restrict__ zero_counter2, uint32_t* __restrict__ zwords, int64_t nzw,
+    int32_t* __restrict__ cell_key) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (zero_counter) *zero_counter = 0;
+    if (zero_counter2) *zero_counter2 = 0;
+  }
+  const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t ts = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = t0; i < nzw; i += ts) zwords[i] = 0u;
+  for (int64_t i = t0; i < cells; i += ts) cell_key[i] = INT_MAX;
+  const int64_t m = *n_occ;
+  for (int64_t q = t0; q < m; q += ts) {
+    const int32_t c = occ[q];
+    if ((int64_t)c >= cells) continue;
+    const unsigned long long v = cmin[c];
+    const int32_t r = (v != ~0ull) ? (int32_t)(uint32_t)v : -1;
+    rep[c] = r;
+    if (r >= 0) parent[r] = r;
+  }
+}
+
 // ---------------------------------------------------------------- union-find
 __device__ __forceinline__ int uf_load(const int32_t* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -3427,6 +3470,125 @@ __global__ __launch_bounds__(kBlock) void k_label_core_orig(const int32_t* __res
   }
 }
 
+// ---- component ids per CELL (all_mutual grids; after k_parent_init_cells and the union passes)
+// Every occupied cell is mutual, so its core points share one component and the component
+// minimum is a per-cell value: cell_key[c] = sorig[root(rep[c])] (cells without core points keep
+// k_parent_init_cells' INT_MAX).  The cell whose representative is the root flags the minimum's
+// bit.  Replaces k_cell_roots + k_ccmin: one thread per occupied cell instead of per point, and
+// no per-point ccmin[] at all (k_label_core_cells reads cell_key through skey).
+// zero: the non-core queue counter of k_label_core_cells (the union passes' list counter until
+// here).
+__global__ __launch_bounds__(kBlock) void k_cell_comp(int32_t* parent,
+                                                     const int32_t* __restrict__ occ,
+                                                     const int32_t* __restrict__ n_occ,
+                                                     int64_t cells,
+                                                     const int32_t* __restrict__ rep,
+                                                     const int32_t* __restrict__ sorig,
+                                                     int32_t* __restrict__ cell_key,
+                                                     uint32_t* __restrict__ min_bits,
+                                                     int32_t* __restrict__ zero) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *zero = 0;
+  const int64_t m = *n_occ;
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < m;
+       q += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t c = occ[q];
+    if ((int64_t)c >= cells) continue;
+    const int r = rep[c];
+    if (r < 0) continue;
+    const int root = uf_find(parent, r);
+    const int32_t k = sorig[root];
+    cell_key[c] = k;
+    if (root == r) atomicOr(min_bits + (k >> 5), 1u << (k & 31));
+  }
+}
+
+// K7/K8 (core points) on all_mutual grids, with the non-core queue folded in: a core point's
+// label is the rank of its CELL's component minimum (cell_key[skey[s]]; sorted points are runs of
+// equal keys, so the lookup is a broadcast load), a non-core point is queued for k_label.
+// ORIG = false: over the sorted points, labels scattered through sorig (as k_label_core);
+// ORIG = true : over the original indices through the inverse permutation spos (as
+//               k_label_core_orig), the key and flag gathered, the queue entry = spos[i].
+// kPU points per thread per tile, loads branch-free level by level, XCD-contiguous tiles (see
+// k_label_core).
+// guard: the box-certain union pass's count of non-mutual cells with core points.  all_mutual
+// promises zero; if it is not, the labels are not valid and the cluster count (written by the
+// scan before this kernel) is replaced by -1, which fails the call at the readback of the count.
+struct AppendSpos {
+  const int32_t* spos;
+  __device__ int32_t operator()(int64_t i) const { return spos[i]; }
+};
+template <bool ORIG>
+__global__ __launch_bounds__(kBlock) void k_label_core_cells(
+    const int32_t* __restrict__ skey, const uint8_t* __restrict__ core,
+    const int32_t* __restrict__ perm, int64_t n, int64_t cells,
+    const int32_t* __restrict__ cell_key, MinRank cid, int32_t* __restrict__ labels,
+    int32_t* __restrict__ nc_list, int32_t* __restrict__ nc_count,
+    const int32_t* __restrict__ guard, int32_t* __restrict__ n_clusters) {
+  if (blockIdx.x == 0 && threadIdx.x == 0 && *guard != 0) *n_clusters = -1;
+  const int64_t T = (n + (int64_t)kBlock * kPU - 1) / ((int64_t)kBlock * kPU);
+  const bool xm = (gridDim.x & 7) == 0;
+  const int64_t xg = blockIdx.x & 7, nbx = gridDim.x >> 3;
+  const int64_t t_lo = xm ? T * xg / 8 : blockIdx.x, t_hi = xm ? T * (xg + 1) / 8 : T;
+  const int64_t t_step = xm ? nbx : gridDim.x;
+  for (int64_t ti = t_lo + (xm ? (int64_t)(blockIdx.x >> 3) : 0); ti < t_hi; ti += t_step) {
+    const int64_t tile = ti * kBlock * kPU;
+    int32_t pv[kPU], k[kPU];
+    uint32_t c[kPU];
+    if (ORIG) {
+#pragma unroll
+      for (int u = 0; u < kPU; ++u)  // streamed once
+        pv[u] = __builtin_nontemporal_load(perm + min(tile + (int64_t)u * kBlock + threadIdx.x,
+                                                       n - 1));
+#pragma unroll
+      for (int u = 0; u < kPU; ++u) {
+        k[u] = skey[pv[u]];
+        c[u] = core[pv[u]];
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < kPU; ++u) {
+        const int64_t s = min(tile + (int64_t)u * kBlock + threadIdx.x, n - 1);
+        k[u] = skey[s];
+        c[u] = core[s];
+        pv[u] = perm[s];
+      }
+    }
+    int32_t own[kPU];
+    uint32_t inb = 0, cb = 0;
+#pragma unroll
+    for (int u = 0; u < kPU; ++u) {
+      const bool in = tile + (int64_t)u * kBlock + threadIdx.x < n;
+      const bool q = in && c[u] != 0u && k[u] >= 0 && (int64_t)k[u] < cells;
+      inb |= in ? (1u << u) : 0u;
+      cb |= (in && c[u] != 0u) ? (1u << u) : 0u;
+      const int32_t v = cell_key[q ? k[u] : 0];  // cells >= 1
+      own[u] = (q && v != INT_MAX) ? v : -1;
+    }
+    uint32_t w[kPU];
+    int32_t pr[kPU];
+#pragma unroll
+    for (int u = 0; u < kPU; ++u) {
+      const int32_t m = own[u] >= 0 ? own[u] : 0;
+      w[u] = cid.bits[m >> 5];
+      pr[u] = cid.pref[m >> 5];
+    }
+#pragma unroll
+    for (int u = 0; u < kPU; ++u) {
+      if (own[u] >= 0) {
+        const int32_t lab = pr[u] + __popc(w[u] & ((1u << (own[u] & 31)) - 1u));
+        if (ORIG)
+          labels[tile + (int64_t)u * kBlock + threadIdx.x] = lab;
+        else
+          labels[pv[u]] = lab;
+      }
+    }
+    if (ORIG)
+      block_append_bits(tile, inb & ~cb, nc_list, nc_count, AppendSpos{perm});
+    else
+      block_append_bits(tile, inb & ~cb, nc_list, nc_count);
+  }
+}
+
 // K7/K8 (non-core points, queued): the smallest component key over adjacent core points, else
 // none.  One wave per point, one lane per candidate cell of its window.  A cell whose box is
 // wholly adjacent contributes its smallest key (cell_key) with no point read; the others are
@@ -3436,7 +3598,10 @@ __global__ __launch_bounds__(kBlock) void k_label_core_orig(const int32_t* __res
 // GLOBAL = false: key = ccmin (component-min original index, local run), label = cid[key];
 // GLOBAL = true : key = slab (the core point's final label: labels are ranks of the sorted global
 //                 representatives, so the smallest label is the smallest representative).
-template <int D, bool GLOBAL, int W = 64>
+// ALLMUT (all_mutual grids, local run): every candidate cell with core points is mutual and key_of
+//                 (ccmin) is not written -- the core flag core_of[j] stands for key_of[j] >= 0, the
+//                 non-mutual search and the mutual[] loads compile out.
+template <int D, bool GLOBAL, int W = 64, bool ALLMUT = false>
 // 6 waves/SIMD (80 VGPRs, no spill; with two candidate points per lane per round 7 spilled 8)
 // W = 32: two points per wave, one per half (the same candidate loads per point, twice the
 // points in flight: the pass is a chain of dependent loads per point, not bandwidth)
@@ -3453,7 +3618,9 @@ __global__ __launch_bounds__(kBlock, 6) void k_label(const float4* __restrict__ 
                                                  const int32_t* __restrict__ nc_list,
                                                  const int32_t* __restrict__ nc_count,
                                                  int32_t* __restrict__ labels,
-                                                 int32_t* __restrict__ kstat = nullptr) {
+                                                 int32_t* __restrict__ kstat = nullptr,
+                                                 const uint8_t* __restrict__ core_of = nullptr) {
+  static_assert(!ALLMUT || (D == 2 && !GLOBAL), "all-mutual grids are 2-D, local runs");
   // kstat (A/B build, RPT_STATS): queued points, points with a core cell in their window, points
   // that searched a partly reachable cell, points labelled
   static_assert(W == 32 || W == 64, "a point per wave or per half-wave");
@@ -3511,7 +3678,7 @@ __global__ __launch_bounds__(kBlock, 6) void k_label(const float4* __restrict__ 
             const CellRec<D> cr = crec[c[k]];
             cb[k] = cr.b;
             ce[k] = cr.e;
-            mu[k] = mutual[c[k]];
+            mu[k] = ALLMUT ? 1 : mutual[c[k]];
             cls[k] = classify<D>(p, rec_boxA<D>(cr), rec_boxB(cr), g);
             if (cls[k] == 1) v = min(v, ck[k]);
           }
@@ -3557,12 +3724,19 @@ __global__ __launch_bounds__(kBlock, 6) void k_label(const float4* __restrict__ 
           const int bl = __shfl(bsel, l), el = __shfl(esel, l);
           // two points per lane per round (their loads issued together): a dense cell costs
           // half the dependent round trips
-          if (__shfl(msel, l)) {  // one component: a single adjacent core point decides
+          if (ALLMUT || __shfl(msel, l)) {  // one component: a single adjacent core point decides
             bool hit = false;
             for (int j0 = bl; j0 < el && !hit; j0 += 2 * W) {
               const int j = j0 + hl, j2 = j + W;
               const bool v1 = j < el, v2 = j2 < el;
-              const int k1 = v1 ? key_of[j] : -1, k2 = v2 ? key_of[j2] : -1;
+              int k1, k2;
+              if (ALLMUT) {
+                k1 = (v1 && core_of[j]) ? 0 : -1;
+                k2 = (v2 && core_of[j2]) ? 0 : -1;
+              } else {
+                k1 = v1 ? key_of[j] : -1;
+                k2 = v2 ? key_of[j2] : -1;
+              }
               const float4 p1 = v1 ? pts[j] : p, p2 = v2 ? pts[j2] : p;
               hit = gbal((k1 >= 0 && adjacent<D>(p, p1, g)) ||
                          (k2 >= 0 && adjacent<D>(p, p2, g))) != 0;
@@ -4281,6 +4455,14 @@ struct DbscanState {
   int32_t* cell_min = nullptr;  // per cell: smallest component key (label pass)
   uint8_t* fok = nullptr;    // per cell: frame condition met by every core point (denoise)
   bool integral_t = false;   // every finite t integral (slab = one frame id)
+  // every occupied cell is mutual by construction: 2-D, one time value per slab (integral times,
+  // ct = 1), every time finite (no isolated cell), the cell diagonal within eps (the cell side
+  // not coarsened by the cell cap), min_samples >= 1.  Set by build_t.
+  bool all_mutual = false;
+  // this run takes the per-cell union init / component ids / core labels (all_mutual grid, the
+  // fused local path with a readback of the cluster count; set by union_pass, read by
+  // labels_local)
+  bool cell_comp = false;
   int64_t* stmp = nullptr;
   Timer tm;
 
@@ -4292,7 +4474,8 @@ struct DbscanState {
                 int64_t n_, double eps_space, double eps_time, int32_t ms, bool timing,
                 hipStream_t st);
   int32_t core_pass(hipStream_t st);
-  int32_t union_pass(hipStream_t st);
+  // fused: called by the fused local path (labels_local follows, the count is read back)
+  int32_t union_pass(hipStream_t st, bool fused = false);
   int32_t labels_local(int32_t* labels, rpt_stdbscan_stats* stats, hipStream_t st);
   // deferred mode: labels_local leaves the cluster count on the device (cid[n]) and the timing
   // events unread; fill_stats completes the stats once the caller has synchronised the stream
@@ -4407,6 +4590,11 @@ int32_t DbscanState::build_t(const float* x, const float* y, const float* z, int
     g.rt = (integral_t && r < 1e9) ? (int)std::min(r, (double)nt) : -1;
     g.tfree = (g.rt >= 0 && ct == 1.0 && (double)g.rt <= std::floor((double)epst)) ? 1 : 0;
   }
+  // a slab is one time value and a cell's diagonal is within eps (margin far above the rounding
+  // of the cell index and of k_cell_box's d2 <= eps2 test), so a cell's points are pairwise
+  // adjacent; a coarsened cell side (cs doubled) fails 2 cs^2 <= eps^2
+  all_mutual = D == 2 && integral_t && ct == 1.0 && hb.n_finite_t == n && min_samples >= 1 &&
+               epst >= 0.f && eps_space > 0.0 && 2.0 * cs * cs <= g.eps2 * (1.0 - 1e-6);
   C = g.cells;
   const int64_t C1 = C + 1;  // + the isolated cell (non-finite t)
   Budget bud;
@@ -4802,7 +4990,8 @@ int32_t DbscanState::core_pass(hipStream_t st) {
   return RPT_OK;
 }
 
-int32_t DbscanState::union_pass(hipStream_t st) {
+int32_t DbscanState::union_pass(hipStream_t st, bool fused) {
+  cell_comp = false;
   if (degenerate) return RPT_OK;
   if (uf_flags < 0) {
     const char* e = ab_env("RPT_UF_FLAGS");
@@ -4839,14 +5028,31 @@ int32_t DbscanState::union_pass(hipStream_t st) {
   const bool nm = dim == 2 && union_pair && union_nm;
   int32_t* nm_list = nm ? cid : nullptr;
   int32_t* nm_count = nm ? cid + n : nullptr;
+  // all_mutual grids on the default 2-D pair path: only the cell representatives' parent
+  // entries are read from here to the label stage (k_union_cells_pair, k_cell_root_snapshot and
+  // k_union_listed start every walk at rep[c]; k_union_nm, which walks the points of non-mutual
+  // cells, has nothing listed and is not launched), so the star initialisation is per cell
+  // (not with the A/B label tiles, which read ccmin, nor with the A/B compression pass:
+  // k_compress walks EVERY core point's parent chain, so it keeps the per-point init)
+  if (uf_compress < 0) {
+    const char* e = ab_env("RPT_UF_COMPRESS");
+    uf_compress = (e && std::atoi(e) == 1) ? 1 : 0;
+  }
+  cell_comp = fused && all_mutual && listing && nm && cell_comp_enabled() && !use_label_tiles() &&
+              !uf_compress;
   // the per-cell minima: from the core pass (cmin_ready) or from the final core flags here
-  hipLaunchKernelGGL(k_init_occ_cells, dim3(gb), dim3(kBlock), 0, st, occ, n_occ, C, rep,
-                     cmin_ready ? nullptr : cmin, pcount, nm_count);
+  if (!cell_comp || !cmin_ready)
+    hipLaunchKernelGGL(k_init_occ_cells, dim3(gb), dim3(kBlock), 0, st, occ, n_occ, C, rep,
+                       cmin_ready ? nullptr : cmin, pcount, nm_count);
   if (!cmin_ready)
     hipLaunchKernelGGL(k_cell_min_pair, dim3(gb), dim3(kBlock), 0, st, skey, core, sorig, n, C,
                        cmin);
-  hipLaunchKernelGGL(k_parent_init_pair, dim3(grid_for(n, kBlock * kPU, 2048)), dim3(kBlock), 0,
-                     st, parent, n, core, skey, mutual, cmin, C, rep);
+  if (cell_comp)
+    hipLaunchKernelGGL(k_parent_init_cells, dim3(gb), dim3(kBlock), 0, st, occ, n_occ, C, cmin,
+                       rep, parent, pcount, nm_count, min_bits, min_words(), cell_min);
+  else
+    hipLaunchKernelGGL(k_parent_init_pair, dim3(grid_for(n, kBlock * kPU, 2048)), dim3(kBlock), 0,
+                       st, parent, n, core, skey, mutual, cmin, C, rep);
   int32_t* lstat_dev = nullptr;  // (A/B diagnostics)
   if (dim == 2) {
     uint4* pm = listing ? pmask : nullptr;
@@ -4882,7 +5088,9 @@ int32_t DbscanState::union_pass(hipStream_t st) {
       hipLaunchKernelGGL((k_union_cells<2, true>), dim3(gw), dim3(kBlock), 0, st, pts, g,
                          cell_start, occ, n_occ, rec<2>(), occ_bits, slab_t, core, rep, mutual,
                          sorig, parent, uf_flags, pm, plist, pcount);
-    if (nm)
+    if (cell_comp) {
+      // no non-mutual cell with core points (nm_count stays 0; k_label_core_cells checks it)
+    } else if (nm)
       hipLaunchKernelGGL(k_union_nm<2>, dim3(gw), dim3(kBlock), 0, st, pts, g, cell_start,
                          rec<2>(), slab_t, core, rep, mutual, sorig, parent, nm_list, nm_count);
     else
@@ -4900,13 +5108,10 @@ int32_t DbscanState::union_pass(hipStream_t st) {
   }
   RPT_CHECK_LAUNCH();
   // every later reader walks to the root with path halving (k_ccmin, k_comp_out, ...), so a
-  // separate compression pass only moves that work; RPT_UF_COMPRESS=1 keeps it (A/B)
-  if (uf_compress < 0) {
-    const char* e = ab_env("RPT_UF_COMPRESS");
-    uf_compress = (e && std::atoi(e) == 1) ? 1 : 0;
-  }
+  // separate compression pass only moves that work; RPT_UF_COMPRESS=1 keeps it (A/B; read
+  // above: it rules the per-cell init out)
 #ifdef RPT_AB
-  if (uf_compress)
+  if (uf_compress && !cell_comp)
     hipLaunchKernelGGL(k_compress, dim3(gb), dim3(kBlock), 0, st, parent, core, n, sorig,
                        (int32_t*)nullptr);
   if (ab_env("RPT_STATS")) {  // A/B diagnostics: the queue and list sizes of this run (syncs)
@@ -4919,6 +5124,9 @@ int32_t DbscanState::union_pass(hipStream_t st) {
                  "[rpt stats] n=%lld occupied=%d listed_cells=%d listed: undecided=%d "
                  "roots_differ=%d searches=%d hits=%d\n",
                  (long long)n, h[0], h[1], ls[0], ls[1], ls[2], ls[3]);
+    // the union init / component / core-label path of this run
+    std::fprintf(stderr, "[rpt stats] n=%lld all_mutual=%d cell_comp=%d\n", (long long)n,
+                 all_mutual ? 1 : 0, cell_comp ? 1 : 0);
   }
 #endif
   RPT_CHECK_LAUNCH();
@@ -4967,16 +5175,38 @@ int32_t DbscanState::labels_local(int32_t* labels, rpt_stdbscan_stats* stats, hi
     return RPT_OK;
   }
   int32_t* nc_count = nc_list + n;
-  // also the per-cell smallest keys (k_cell_min_key fused; cell_min filled with INT_MAX by
-  // cluster_ids' first kernel) and nc_count cleared
-  RPT_TRY(cluster_ids(st, cell_min, nc_count));
   const MinRank mr{min_bits, min_pref};
-  if (spos_on)
-    hipLaunchKernelGGL(k_label_core_orig, dim3((grid_for(n, kBlock * kPU, 2048) + 7) & ~7),
-                       dim3(kBlock), 0, st, ccmin, n, slab, mr, labels);
-  else
-    hipLaunchKernelGGL(k_label_core, dim3((grid_for(n, kBlock * kPU, 2048) + 7) & ~7),
-                       dim3(kBlock), 0, st, ccmin, n, sorig, mr, labels);
+  const unsigned glc = (unsigned)((grid_for(n, kBlock * kPU, 2048) + 7) & ~7);
+  if (cell_comp) {
+    // component ids per occupied cell (minimum bits and cell_min = INT_MAX cleared by
+    // k_parent_init_cells), the rank prefix, then core labels + the non-core queue in one
+    // per-point pass; ccmin is not written.  cid[n]: the union pass's non-mutual-cell count
+    const int64_t W = min_words();
+    hipLaunchKernelGGL(k_cell_comp, dim3(grid_for(n, kBlock, 2048)), dim3(kBlock), 0, st, parent,
+                       occ, n_occ_dev, C, rep, sorig, cell_min, min_bits, nc_count);
+    hipLaunchKernelGGL(k_word_popc, dim3(grid_for(W, kBlock, 2048)), dim3(kBlock), 0, st,
+                       min_bits, W, min_pref);
+    RPT_CHECK_LAUNCH();
+    RPT_TRY(exclusive_scan_total_i32(min_pref, min_pref, W, st));
+    if (spos_on)
+      hipLaunchKernelGGL(k_label_core_cells<true>, dim3(glc), dim3(kBlock), 0, st, skey, core,
+                         slab, n, C, cell_min, mr, labels, nc_list, nc_count, cid + n,
+                         n_clusters_ptr());
+    else
+      hipLaunchKernelGGL(k_label_core_cells<false>, dim3(glc), dim3(kBlock), 0, st, skey, core,
+                         sorig, n, C, cell_min, mr, labels, nc_list, nc_count, cid + n,
+                         n_clusters_ptr());
+  } else {
+    // also the per-cell smallest keys (k_cell_min_key fused; cell_min filled with INT_MAX by
+    // cluster_ids' first kernel) and nc_count cleared
+    RPT_TRY(cluster_ids(st, cell_min, nc_count));
+    if (spos_on)
+      hipLaunchKernelGGL(k_label_core_orig, dim3(glc), dim3(kBlock), 0, st, ccmin, n, slab, mr,
+                         labels);
+    else
+      hipLaunchKernelGGL(k_label_core, dim3(glc), dim3(kBlock), 0, st, ccmin, n, sorig, mr,
+                         labels);
+  }
   int32_t* kstat = nullptr;  // (A/B diagnostics)
 #ifdef RPT_AB
   if (ab_env("RPT_STATS")) {  // (a leaked 16 B per process)
@@ -4992,13 +5222,22 @@ int32_t DbscanState::labels_local(int32_t* labels, rpt_stdbscan_stats* stats, hi
                        g, tile_R, tile_by, tile_nbands, (int64_t)g.nt * tile_nbands, occ,
                        n_occ_dev, rowq, rec<2>(), mutual, occ_bits, slab_t, pts, ccmin, cell_min,
                        sorig, mr, min_samples, labels);
+  else if (cell_comp && label_w() == 64)
+    hipLaunchKernelGGL((k_label<2, false, 64, true>), dim3(wave_grid(n)), dim3(kBlock), 0, st,
+                       pts, skey, g, rec<2>(), occ_bits, slab_t, (const int32_t*)nullptr,
+                       cell_min, mutual, sorig, mr, nc_list, nc_count, labels,
+                       (int32_t*)nullptr, core);
   else if (dim == 2 && label_w() == 64)
     hipLaunchKernelGGL((k_label<2, false, 64>), dim3(wave_grid(n)), dim3(kBlock), 0, st, pts,
                        skey, g, rec<2>(), occ_bits, slab_t, ccmin, cell_min, mutual, sorig, mr,
                        nc_list, nc_count, labels);
   else
 #endif
-  if (dim == 2)
+  if (cell_comp)
+    hipLaunchKernelGGL((k_label<2, false, 32, true>), dim3(wave_grid(n)), dim3(kBlock), 0, st,
+                       pts, skey, g, rec<2>(), occ_bits, slab_t, (const int32_t*)nullptr,
+                       cell_min, mutual, sorig, mr, nc_list, nc_count, labels, kstat, core);
+  else if (dim == 2)
     hipLaunchKernelGGL((k_label<2, false, 32>),
                        dim3(wave_grid(n)), dim3(kBlock), 0, st, pts, skey, g,
                        rec<2>(), occ_bits, slab_t, ccmin, cell_min, mutual, sorig, mr, nc_list,
@@ -5031,6 +5270,10 @@ int32_t DbscanState::labels_local(int32_t* labels, rpt_stdbscan_stats* stats, hi
 }
 
 int32_t DbscanState::fill_stats(int32_t ncl, rpt_stdbscan_stats* stats) {
+  if (ncl < 0) {  // k_label_core_cells' guard
+    set_error("rpt_stdbscan: a non-mutual cell on a grid taken for all-mutual (labels invalid)");
+    return RPT_EHIP;
+  }
   {
     stats->n_points = n;
     stats->n_clusters = ncl;
@@ -5230,7 +5473,7 @@ int32_t stdbscan(const float* x, const float* y, const float* z, int64_t stride,
   RPT_TRY(S->build(x, y, z, stride, t, n, eps_space, eps_time, min_samples,
                    stats && stats->timing, st));
   RPT_TRY(S->core_pass(st));
-  RPT_TRY(S->union_pass(st));
+  RPT_TRY(S->union_pass(st, stats != nullptr));  // (the guard needs labels_local's readback)
   return S->labels_local(labels, stats, st);
 }
 
@@ -5349,7 +5592,7 @@ int32_t stdbscan_deferred(const float* x, const float* y, const float* z, int64_
   S->given_bounds = nullptr;
   RPT_TRY(sb);
   RPT_TRY(S->core_pass(st));
-  RPT_TRY(S->union_pass(st));
+  RPT_TRY(S->union_pass(st, true));
   S->defer = !S->degenerate;
   const int32_t s_ = S->labels_local(labels, stats, st);
   *n_clusters_dev = S->defer ? S->n_clusters_ptr() : nullptr;

@@ -1,6 +1,8 @@
 #!/bin/bash
 # Same-box A/B of the in-tree librpt against abl/librpt_base.so (a copy of an earlier build) on
 # the bench at FR frames, interleaved: new, base, new, base.  Optional TESTS=... runs first.
+# PLAIN=1: the plain bench line (default frames, steps and warm-up, no --full legs; the leg
+# switches left on the command act only with --full); also prints steady_state.
 set -o pipefail
 cd "$(dirname "$0")/.." || exit 1
 mkdir -p gpurun_out
@@ -11,15 +13,18 @@ if [ -n "$TESTS" ]; then
   tail -2 gpurun_out/gpu_sel.log
 fi
 FR=${FR:-1000}
+BARGS=(--full --total-frames $FR --steps 20 --warmup 3)
+[ -n "$PLAIN" ] && BARGS=()
 run() {  # tag env...
   local tag=$1; shift
-  env "$@" timeout -k 10 240 python bench.py --full --total-frames $FR --steps 20 --warmup 3 \
+  env "$@" timeout -k 10 240 python bench.py "${BARGS[@]}" \
     --no-cpu-baseline --h2d-steps 0 > gpurun_out/ab_$tag.json 2> gpurun_out/ab_$tag.err || return 1
   python - "$tag" <<'PY'
 import json, sys
 t = sys.argv[1]
 d = json.loads(open(f"gpurun_out/ab_{t}.json").read().strip().splitlines()[-1])
-print(t, d["value"], d["ms_per_step"], d.get("one_stack_in_flight", {}).get("ms_per_step"), d["stage_ms"])
+print(t, d["value"], d["ms_per_step"], (d.get("one_stack_in_flight") or {}).get("ms_per_step"),
+      d.get("steady_state"), d["stage_ms"])
 PY
 }
 run new1 RPT_AB=new || exit 1
