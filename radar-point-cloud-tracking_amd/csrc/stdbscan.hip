@@ -19,7 +19,8 @@
 //   k_bounds      min/max per dimension and time, "times integral" flag        (1 sync)
 //   k_keys        cell key per point: ((slab*nz + cz)*ny + cy)*nx + cx
 //   radix sort    stable, so every cell lists its points in index order
-//   k_gather      sorted float4 {x, y, z|t, t} + original index
+//   k_gather      sorted float4 {x, y, z|t, t} + original index (the slab writers: float2 {x, y}
+//                 where no kernel of the run needs a point's time, DbscanState::xy_points)
 //   k_cell_count  -> exclusive scan -> cell_start[C+1]
 //   k_cell_box    per occupied cell: bounding box in space and time, "mutual" flag
 //                 (box diagonal within eps and time span within eps_t: every pair adjacent)
@@ -347,6 +348,45 @@ __device__ __forceinline__ int slab_of(float t, const Geom& g) {
   return cell_of((double)t, g.ot, g.inv_ct, g.nt);
 }
 
+// A sorted point: float4 {x, y, z|t, t}, or float2 {x, y} where no kernel of the run needs a
+// point's time (XY; DbscanState::xy_points: Geom::tfree windows, one time value per slab, which
+// the cell records and slab_t carry).  load_pt's z / w are NaN in xy form: a time test that
+// reached them would pass for no pair.
+template <bool XY>
+struct PtRec {
+  using type = float4;
+};
+template <>
+struct PtRec<true> {
+  using type = float2;
+};
+template <bool XY>
+using Pt = typename PtRec<XY>::type;
+template <bool XY>
+__device__ __forceinline__ float4 load_pt(const Pt<XY>* __restrict__ pts, int64_t i) {
+  if constexpr (XY) {
+    const float2 v = pts[i];
+    return make_float4(v.x, v.y, NAN, NAN);
+  } else {
+    return pts[i];
+  }
+}
+template <bool XY>
+__device__ __forceinline__ void store_pt(Pt<XY>* __restrict__ pts, int64_t i, float x, float y,
+                                         float t) {
+  if constexpr (XY)
+    pts[i] = make_float2(x, y);
+  else
+    pts[i] = make_float4(x, y, t, t);
+}
+// xy form: the writer's own per-slab time range (what k_slab_range derives from the cell records
+// otherwise): the slab's one time value read from its first point, (FLT_MAX, -FLT_MAX) when empty
+__device__ __forceinline__ float2 slab_time_of(const float* __restrict__ t, int lo, int hi) {
+  if (lo >= hi) return make_float2(FLT_MAX, -FLT_MAX);
+  const float v = t[lo];
+  return make_float2(v, v);
+}
+
 template <int D>
 __global__ __launch_bounds__(kBlock) void k_keys(const float* __restrict__ x,
                                                 const float* __restrict__ y,
@@ -545,13 +585,15 @@ __global__ void k_slab_lo(const float* __restrict__ t, int64_t n, Geom g,
   }
 }
 
+// XY: float2 points, no per-point time load; slab_t[s] written here (see slab_time_of)
+template <bool XY>
 __global__ __launch_bounds__(kBucketBlock) void k_slab_bucket(
     const float* __restrict__ x, const float* __restrict__ y, int64_t stride,
     const float* __restrict__ t, Geom g, const int32_t* __restrict__ slab_lo,
-    float4* __restrict__ pts, int32_t* __restrict__ sorig, int32_t* __restrict__ skey,
+    Pt<XY>* __restrict__ pts, int32_t* __restrict__ sorig, int32_t* __restrict__ skey,
     int32_t* __restrict__ spos, int32_t* __restrict__ cell_start, int32_t* __restrict__ occ_tmp,
     int32_t* __restrict__ slab_occ, uint32_t* __restrict__ occ_bits,
-    unsigned long long* __restrict__ cmin_all = nullptr) {
+    unsigned long long* __restrict__ cmin_all, float2* __restrict__ slab_t) {
   // the slab's nx * ny cell counts, sized at launch (a 463-m sweep at cells of 5.6 m: 27 KiB, so
   // several slabs share a CU instead of one 64-KiB histogram each)
   // cmin_all (nullable; the fused K5): every occupied cell's (min original, sorted) pair over all
@@ -563,6 +605,7 @@ __global__ __launch_bounds__(kBucketBlock) void k_slab_bucket(
   const int P = g.nx * g.ny;
   int32_t* mn = hist + P;  // (cmin_all only: the launch sizes 2P words)
   const int lo = slab_lo[s], hi = slab_lo[s + 1];
+  if (XY && threadIdx.x == 0) slab_t[s] = slab_time_of(t, lo, hi);
   for (int c = threadIdx.x; c < P; c += kBucketBlock) {
     hist[c] = 0;
     if (cmin_all) mn[c] = INT_MAX;
@@ -675,7 +718,7 @@ __global__ __launch_bounds__(kBucketBlock) void k_slab_bucket(
       const int i = min(i0 + u * kBucketBlock + (int)threadIdx.x, hi - 1);  // branch-free
       px[u] = x[(int64_t)i * stride];
       py[u] = y[(int64_t)i * stride];
-      pt[u] = t[i];
+      pt[u] = XY ? 0.f : t[i];
     }
 #pragma unroll
     for (int u = 0; u < kBucketU; ++u) {
@@ -688,7 +731,7 @@ __global__ __launch_bounds__(kBucketBlock) void k_slab_bucket(
       base = __shfl(base, head, 64);
       if (v) {
         const int dst = lo + base + rank;
-        pts[dst] = make_float4(px[u], py[u], pt[u], pt[u]);
+        store_pt<XY>(pts, dst, px[u], py[u], pt[u]);
         sorig[dst] = i;
         if (spos) spos[i] = dst;  // (kernel-uniform; coalesced: i runs over the lanes)
         skey[dst] = s * P + c;
@@ -879,17 +922,20 @@ __global__ void k_occ_write(const int32_t* __restrict__ occf, const int32_t* __r
     if (occf[k]) occ[pos[k]] = (int32_t)k;
 }
 
+// XY: as k_slab_bucket<true> (a slab's first chunk writes slab_t[s])
+template <bool XY>
 __global__ __launch_bounds__(kBucketBlock) void k_slab_chunk_scatter(
     const float* __restrict__ x, const float* __restrict__ y, int64_t stride,
     const float* __restrict__ t, Geom g, const int32_t* __restrict__ slab_lo, int CH,
-    const int32_t* __restrict__ hist_g, float4* __restrict__ pts, int32_t* __restrict__ sorig,
-    int32_t* __restrict__ skey, int32_t* __restrict__ spos) {
+    const int32_t* __restrict__ hist_g, Pt<XY>* __restrict__ pts, int32_t* __restrict__ sorig,
+    int32_t* __restrict__ skey, int32_t* __restrict__ spos, float2* __restrict__ slab_t) {
   extern __shared__ int32_t cur[];
   const int s = blockIdx.x / CH, ch = blockIdx.x - s * CH;
   const int P = g.nx * g.ny;
   int lo, hi;
   slab_chunk(slab_lo, s, ch, CH, lo, hi);
   const int base = slab_lo[s];
+  if (XY && ch == 0 && threadIdx.x == 0) slab_t[s] = slab_time_of(t, base, slab_lo[s + 1]);
   const int32_t* hc = hist_g + (int64_t)blockIdx.x * P;
   for (int c = threadIdx.x; c < P; c += kBucketBlock) cur[c] = hc[c];
   __syncthreads();
@@ -900,7 +946,7 @@ __global__ __launch_bounds__(kBucketBlock) void k_slab_chunk_scatter(
       const int i = min(i0 + u * kBucketBlock + (int)threadIdx.x, hi - 1);  // branch-free
       px[u] = x[(int64_t)i * stride];
       py[u] = y[(int64_t)i * stride];
-      pt[u] = t[i];
+      pt[u] = XY ? 0.f : t[i];
     }
 #pragma unroll
     for (int u = 0; u < kBucketU; ++u) {
@@ -909,7 +955,7 @@ __global__ __launch_bounds__(kBucketBlock) void k_slab_chunk_scatter(
         const int c = cell_of((double)py[u], g.oy, g.inv_cs, g.ny) * g.nx +
                       cell_of((double)px[u], g.ox, g.inv_cs, g.nx);
         const int dst = base + atomicAdd(&cur[c], 1);
-        pts[dst] = make_float4(px[u], py[u], pt[u], pt[u]);
+        store_pt<XY>(pts, dst, px[u], py[u], pt[u]);
         sorig[dst] = i;
         if (spos) spos[i] = dst;  // (kernel-uniform; coalesced: i runs over the lanes)
         skey[dst] = s * P + c;
@@ -1020,9 +1066,11 @@ __device__ __forceinline__ float4 rec_boxB(const CellRec<3>& r) {
 // 16 lanes 347 / 321, 32 lanes 453 / 387.  mutual[c] = 1 when every pair of points in the cell
 // passes the neighbour test (computed conservatively from the box with the same rounding as the
 // pair test).
+// XY (2-D, float2 points): the time fields come from the slab's one time value (slab_t, filled by
+// the grid build's writer), not from a reduction over equal values.
 constexpr int kCbLanes = 16;
-template <int D>
-__global__ __launch_bounds__(kBlock) void k_cell_box(const float4* __restrict__ pts,
+template <int D, bool XY = false>
+__global__ __launch_bounds__(kBlock) void k_cell_box(const Pt<XY>* __restrict__ pts,
                                                     const int32_t* __restrict__ cell_start,
                                                     const int32_t* __restrict__ occ,
                                                     const int32_t* __restrict__ n_occ, Geom g,
@@ -1030,7 +1078,9 @@ __global__ __launch_bounds__(kBlock) void k_cell_box(const float4* __restrict__ 
                                                     CellRec<D>* __restrict__ crec,
                                                     unsigned long long* __restrict__ cmin =
                                                         nullptr,
-                                                    const int32_t* __restrict__ sorig = nullptr) {
+                                                    const int32_t* __restrict__ sorig = nullptr,
+                                                    const float2* __restrict__ slab_t = nullptr) {
+  static_assert(!XY || D == 2, "xy points are 2-D");
   // sorig (kernel-uniform): cmin[c] = the (min original, sorted) pair over ALL the cell's points
   // (the fused K5 keeps it for all-core cells), read alongside the points; otherwise none (~0)
   constexpr int L = kCbLanes;
@@ -1059,7 +1109,7 @@ __global__ __launch_bounds__(kBlock) void k_cell_box(const float4* __restrict__ 
       for (int u = 0; u < kU; ++u) {
         const int s2 = s0 + L * u;
         const int sc = (s2 < e) ? s2 : s0;  // duplicates of a cell point leave the box as is
-        pp[u] = pts[sc];
+        pp[u] = load_pt<XY>(pts, sc);
         if (sorig) so[u] = (uint32_t)sorig[sc];
       }
 #pragma unroll
@@ -1067,8 +1117,10 @@ __global__ __launch_bounds__(kBlock) void k_cell_box(const float4* __restrict__ 
         const float4 p = pp[u];
         x0 = fminf(x0, p.x); x1 = fmaxf(x1, p.x);
         y0 = fminf(y0, p.y); y1 = fmaxf(y1, p.y);
-        z0 = fminf(z0, p.z); z1 = fmaxf(z1, p.z);
-        t0 = fminf(t0, p.w); t1 = fmaxf(t1, p.w);
+        if constexpr (!XY) {
+          z0 = fminf(z0, p.z); z1 = fmaxf(z1, p.z);
+          t0 = fminf(t0, p.w); t1 = fmaxf(t1, p.w);
+        }
         if (sorig) {
           const int s2 = s0 + L * u;
           const uint64_t v = ((uint64_t)so[u] << 32) | (uint32_t)((s2 < e) ? s2 : s0);
@@ -1080,8 +1132,12 @@ __global__ __launch_bounds__(kBlock) void k_cell_box(const float4* __restrict__ 
     if (sorig) mn = row_reduce<L>(mn, OpMin{});
     x0 = row_reduce<L>(x0, OpMin{}); x1 = row_reduce<L>(x1, OpMax{});
     y0 = row_reduce<L>(y0, OpMin{}); y1 = row_reduce<L>(y1, OpMax{});
-    z0 = row_reduce<L>(z0, OpMin{}); z1 = row_reduce<L>(z1, OpMax{});
-    t0 = row_reduce<L>(t0, OpMin{}); t1 = row_reduce<L>(t1, OpMax{});
+    if constexpr (XY) {
+      t0 = t1 = slab_t[g.slab_of_key(c)].x;
+    } else {
+      z0 = row_reduce<L>(z0, OpMin{}); z1 = row_reduce<L>(z1, OpMax{});
+      t0 = row_reduce<L>(t0, OpMin{}); t1 = row_reduce<L>(t1, OpMax{});
+    }
     if (D != 3) {
       z0 = t0;  // 2-D: pts[].z carries t (unused by the 2-D tests)
       z1 = t1;
@@ -1154,8 +1210,8 @@ __device__ __forceinline__ void cell_box_store(int c, int b, int e, float x0, fl
   if (cmin) cmin[c] = has_mn ? mn : ~0ull;  // the core pass's per-cell minima
 }
 
-template <int D>
-__global__ __launch_bounds__(kBlock) void k_cell_box_mixed(const float4* __restrict__ pts,
+template <int D, bool XY = false>
+__global__ __launch_bounds__(kBlock) void k_cell_box_mixed(const Pt<XY>* __restrict__ pts,
                                                           const int32_t* __restrict__ cell_start,
                                                           const int32_t* __restrict__ occ,
                                                           const int32_t* __restrict__ n_occ,
@@ -1164,7 +1220,10 @@ __global__ __launch_bounds__(kBlock) void k_cell_box_mixed(const float4* __restr
                                                           unsigned long long* __restrict__ cmin =
                                                               nullptr,
                                                           const int32_t* __restrict__ sorig =
+                                                              nullptr,
+                                                          const float2* __restrict__ slab_t =
                                                               nullptr) {
+  static_assert(!XY || D == 2, "xy points are 2-D");
   constexpr int L = kCbLanes;
   const int lane = threadIdx.x & 63;
   const int grp = lane / L, j = lane & (L - 1);
@@ -1184,19 +1243,22 @@ __global__ __launch_bounds__(kBlock) void k_cell_box_mixed(const float4* __restr
 #pragma unroll
       for (int u = 0; u < kCbSmall; ++u) {
         const int sc = (b + u < e) ? b + u : b;  // duplicates of a cell point leave the box as is
-        pp[u] = pts[sc];
+        pp[u] = load_pt<XY>(pts, sc);
         if (sorig) so[u] = (uint32_t)sorig[sc];
       }
       float x0 = FLT_MAX, x1 = -FLT_MAX, y0 = FLT_MAX, y1 = -FLT_MAX;
       float z0 = FLT_MAX, z1 = -FLT_MAX, t0 = FLT_MAX, t1 = -FLT_MAX;
+      if constexpr (XY) t0 = t1 = slab_t[g.slab_of_key(c)].x;
       uint64_t mn = ~0ull;
 #pragma unroll
       for (int u = 0; u < kCbSmall; ++u) {
         const float4 p = pp[u];
         x0 = fminf(x0, p.x); x1 = fmaxf(x1, p.x);
         y0 = fminf(y0, p.y); y1 = fmaxf(y1, p.y);
-        z0 = fminf(z0, p.z); z1 = fmaxf(z1, p.z);
-        t0 = fminf(t0, p.w); t1 = fmaxf(t1, p.w);
+        if constexpr (!XY) {
+          z0 = fminf(z0, p.z); z1 = fmaxf(z1, p.z);
+          t0 = fminf(t0, p.w); t1 = fmaxf(t1, p.w);
+        }
         if (sorig) {
           const uint64_t v = ((uint64_t)so[u] << 32) | (uint32_t)((b + u < e) ? b + u : b);
           mn = v < mn ? v : mn;
@@ -1235,7 +1297,7 @@ __global__ __launch_bounds__(kBlock) void k_cell_box_mixed(const float4* __restr
         for (int u = 0; u < kU; ++u) {
           const int s2 = s0 + L * u;
           const int sc = (s2 < ee) ? s2 : s0;
-          pp[u] = pts[sc];
+          pp[u] = load_pt<XY>(pts, sc);
           if (sorig) so[u] = (uint32_t)sorig[sc];
         }
 #pragma unroll
@@ -1243,8 +1305,10 @@ __global__ __launch_bounds__(kBlock) void k_cell_box_mixed(const float4* __restr
           const float4 p = pp[u];
           x0 = fminf(x0, p.x); x1 = fmaxf(x1, p.x);
           y0 = fminf(y0, p.y); y1 = fmaxf(y1, p.y);
-          z0 = fminf(z0, p.z); z1 = fmaxf(z1, p.z);
-          t0 = fminf(t0, p.w); t1 = fmaxf(t1, p.w);
+          if constexpr (!XY) {
+            z0 = fminf(z0, p.z); z1 = fmaxf(z1, p.z);
+            t0 = fminf(t0, p.w); t1 = fmaxf(t1, p.w);
+          }
           if (sorig) {
             const int s2 = s0 + L * u;
             const uint64_t v = ((uint64_t)so[u] << 32) | (uint32_t)((s2 < ee) ? s2 : s0);
@@ -1255,8 +1319,12 @@ __global__ __launch_bounds__(kBlock) void k_cell_box_mixed(const float4* __restr
       if (sorig) mn = row_reduce<L>(mn, OpMin{});
       x0 = row_reduce<L>(x0, OpMin{}); x1 = row_reduce<L>(x1, OpMax{});
       y0 = row_reduce<L>(y0, OpMin{}); y1 = row_reduce<L>(y1, OpMax{});
-      z0 = row_reduce<L>(z0, OpMin{}); z1 = row_reduce<L>(z1, OpMax{});
-      t0 = row_reduce<L>(t0, OpMin{}); t1 = row_reduce<L>(t1, OpMax{});
+      if constexpr (XY) {
+        t0 = t1 = slab_t[g.slab_of_key(cc)].x;
+      } else {
+        z0 = row_reduce<L>(z0, OpMin{}); z1 = row_reduce<L>(z1, OpMax{});
+        t0 = row_reduce<L>(t0, OpMin{}); t1 = row_reduce<L>(t1, OpMax{});
+      }
       if (D != 3) {
         z0 = t0;
         z1 = t1;
@@ -1317,9 +1385,11 @@ __global__ __launch_bounds__(kBlock) void k_slab_range(const CellRec<D>* __restr
 // within a few 2^-24 of the float64 one (relative), far inside the 1e-5 margins, so only pairs
 // within 1e-5 of eps reach the float64 test -- the float64 ops (half rate, plus conversions) were
 // most of the VALU of the pair-testing kernels.
-template <int D>
+// XY (points loaded from the float2 layout: Geom::tfree windows, every pair within eps_t): x and
+// y only.
+template <int D, bool XY = false>
 __device__ __forceinline__ bool adjacent(const float4& a, const float4& b, const Geom& g) {
-  const float dt = fabsf(a.w - b.w);
+  const float dt = XY ? 0.f : fabsf(a.w - b.w);
   const float fx = a.x - b.x, fy = a.y - b.y;
   float f2 = fx * fx + fy * fy;
   if (D == 3) {
@@ -1338,7 +1408,7 @@ __device__ __forceinline__ bool adjacent(const float4& a, const float4& b, const
     }
     in = d2 <= g.eps2;
   }
-  return in && (dt <= g.epst);
+  return XY ? in : (in && (dt <= g.epst));
 }
 
 // |p - [lo, hi]| lower bound and the farthest-end distance, float64, each rounded like the pair
@@ -1351,14 +1421,18 @@ __device__ __forceinline__ void span_dist(float p, float lo, float hi, double& d
 }
 
 // 0: no point of the cell can be adjacent; 1: every point is adjacent; 2: test pairs.
-template <int D>
+// XY: as adjacent<D, true>, no time bounds (the cell comes from the point's tfree window).
+template <int D, bool XY = false>
 __device__ __forceinline__ int classify(const float4& p, const float4& A, const float4& B,
                                         const Geom& g) {
   // time (float32, same rounding as the pair test)
-  const float tlo = B.z, thi = B.w;
-  const float tmin = (p.w < tlo) ? (tlo - p.w) : ((p.w > thi) ? (p.w - thi) : 0.f);
-  if (!(tmin <= g.epst)) return 0;
-  const float tmax = fmaxf(fabsf(p.w - tlo), fabsf(p.w - thi));
+  float tmax = 0.f;
+  if constexpr (!XY) {
+    const float tlo = B.z, thi = B.w;
+    const float tmin = (p.w < tlo) ? (tlo - p.w) : ((p.w > thi) ? (p.w - thi) : 0.f);
+    if (!(tmin <= g.epst)) return 0;
+    tmax = fmaxf(fabsf(p.w - tlo), fabsf(p.w - thi));
+  }
   {
     // float32 screen of the spatial bounds (as adjacent / classify_cells): float64 only when a
     // bound lies within 1e-5 of eps^2
@@ -1571,6 +1645,20 @@ __device__ __forceinline__ Window make_window(int cx, int cy, int cz, float tlo,
   return w;
 }
 
+// make_window<D, false> of a point of slab s on integral times (g.rt >= 0), from the slab itself
+// (xy points carry no time; slab_of(t) of a point is its key's slab)
+template <int D>
+__device__ __forceinline__ Window slab_window(int cx, int cy, int cz, int s, const Geom& g) {
+  Window w;
+  w.s0 = max(s - g.rt, 0);
+  w.nS = max(min(s + g.rt, g.nt - 1) - w.s0 + 1, 0);
+  w.x0 = cx - 2;
+  w.y0 = cy - 2;
+  w.z0 = (D == 3) ? cz - 2 : 0;
+  w.total = w.nS * ((D == 3) ? 125 : 25);
+  return w;
+}
+
 template <int D>
 __device__ __forceinline__ void decode_key(int64_t key, const Geom& g, int& cx, int& cy, int& cz) {
   // keys of real cells are < 2^30 (cmax): 32-bit divisions, not the 64-bit ones' call sequence
@@ -1601,7 +1689,9 @@ __device__ __forceinline__ int64_t window_cell(const Window& w, int q, const Geo
   return (((int64_t)sl * g.nz + z) * g.ny + y) * g.nx + x;
 }
 
+template <bool XY = false>
 __device__ __forceinline__ float4 shfl_f4(const float4& v, int l) {
+  if constexpr (XY) return make_float4(__shfl(v.x, l), __shfl(v.y, l), NAN, NAN);
   return make_float4(__shfl(v.x, l), __shfl(v.y, l), __shfl(v.z, l), __shfl(v.w, l));
 }
 
@@ -2330,8 +2420,9 @@ __device__ __forceinline__ int mask_pos_key(int pos, const Geom& g, int R, int W
   const int y = cy + cw_row(k) - 2;
   return (s2 * g.ny + y) * g.nx + (cx - 2 + dx);
 }
+template <bool XY>
 __global__ __launch_bounds__(kBlock, 8) void k_core_slow_masked(
-    const float4* __restrict__ pts, Geom g, int R, const CellRec<2>* __restrict__ crec,
+    const Pt<XY>* __restrict__ pts, Geom g, int R, const CellRec<2>* __restrict__ crec,
     const int32_t* __restrict__ occ, const int32_t* __restrict__ slow,
     const int32_t* __restrict__ slowq, const int32_t* __restrict__ n_slow,
     const uint4* __restrict__ pmask, const int32_t* __restrict__ clo, uint8_t* __restrict__ core,
@@ -2345,7 +2436,7 @@ __global__ __launch_bounds__(kBlock, 8) void k_core_slow_masked(
     const int s = slow[q];
     const int32_t cq = slowq[q];
     // all independent of each other: one round of memory latency
-    const float4 p = pts[s];
+    const float4 p = load_pt<XY>(pts, s);
     const int32_t key = occ[cq];
     const uint4 m = pmask[cq];
     int cnt = clo[cq];
@@ -2357,8 +2448,8 @@ __global__ __launch_bounds__(kBlock, 8) void k_core_slow_masked(
     const int k0 = h0 ? mask_pos_key(lane, g, R, W, mg, cx, cy, cs) : key;
     const int k1 = h1 ? mask_pos_key(lane + 64, g, R, W, mg, cx, cy, cs) : key;
     const CellRec<2> c0 = crec[k0], c1 = crec[k1];  // (branch-free: the own record otherwise)
-    const int cl0 = h0 ? classify<2>(p, rec_boxA<2>(c0), rec_boxB(c0), g) : 0;
-    const int cl1 = h1 ? classify<2>(p, rec_boxA<2>(c1), rec_boxB(c1), g) : 0;
+    const int cl0 = h0 ? classify<2, XY>(p, rec_boxA<2>(c0), rec_boxB(c0), g) : 0;
+    const int cl1 = h1 ? classify<2, XY>(p, rec_boxA<2>(c1), rec_boxB(c1), g) : 0;
     int add = (cl0 == 1 ? c0.e - c0.b : 0) + (cl1 == 1 ? c1.e - c1.b : 0);
     int may = (cl0 == 2 ? c0.e - c0.b : 0) + (cl1 == 2 ? c1.e - c1.b : 0);
     cnt += wave_sum(add);
@@ -2374,7 +2465,7 @@ __global__ __launch_bounds__(kBlock, 8) void k_core_slow_masked(
           const int bb = __shfl(bq, l), ee = __shfl(eq, l);
           for (int j0 = bb; j0 < ee && cnt < need; j0 += 64) {
             const int jj = j0 + lane;
-            const bool a = (jj < ee) && adjacent<2>(p, pts[jj], g);
+            const bool a = (jj < ee) && adjacent<2, XY>(p, load_pt<XY>(pts, jj), g);
             cnt += __popcll(__ballot(a));
           }
         }
@@ -2985,7 +3076,8 @@ __global__ __launch_bounds__(kBlock) void k_cell_root_snapshot(const int32_t* __
 // pair whose roots still differ.  Without the kR-wide enumeration the kernel holds far fewer
 // registers than k_union_cells<2, true> (twice the waves per SIMD: the pass is a chain of
 // dependent loads per cell).
-__global__ __launch_bounds__(kBlock) void k_union_listed(const float4* __restrict__ pts, Geom g,
+template <bool XY>
+__global__ __launch_bounds__(kBlock) void k_union_listed(const Pt<XY>* __restrict__ pts, Geom g,
                                                         const int32_t* __restrict__ occ,
                                                         const CellRec<2>* __restrict__ crec,
                                                         const uint32_t* __restrict__ occ_bits,
@@ -3059,8 +3151,8 @@ __global__ __launch_bounds__(kBlock) void k_union_listed(const float4* __restric
           float4 pb = make_float4(0.f, 0.f, 0.f, 0.f);
           bool cb_ok = false;
           if (jb < ebl && core[jb]) {
-            pb = pts[jb];
-            cb_ok = classify<2>(pb, A1, A2, g) != 0;
+            pb = load_pt<XY>(pts, jb);
+            cb_ok = classify<2, XY>(pb, A1, A2, g) != 0;
           }
           // this chunk's B core points that can reach A's box (bm) against A's core points 64
           // at a time: each lane loads ONE A point per chunk and tests it against every such B
@@ -3070,14 +3162,14 @@ __global__ __launch_bounds__(kBlock) void k_union_listed(const float4* __restric
           for (int ja0 = ba; bm && ja0 < ea && !hit; ja0 += 64) {
             const int ja = ja0 + lane;
             const bool va = (ja < ea) && core[ja];
-            const float4 pa = va ? pts[ja] : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 pa = va ? load_pt<XY>(pts, ja) : make_float4(0.f, 0.f, 0.f, 0.f);
             bool adj = false;
             uint64_t rest = bm;
             while (rest) {  // (wave-uniform)
               const int lb = __ffsll((unsigned long long)rest) - 1;
               rest &= rest - 1;
-              const float4 pq = shfl_f4(pb, lb);
-              adj = adj || (va && adjacent<2>(pq, pa, g));
+              const float4 pq = shfl_f4<XY>(pb, lb);
+              adj = adj || (va && adjacent<2, XY>(pq, pa, g));
             }
             hit = __ballot(adj) != 0;
           }
@@ -3601,11 +3693,12 @@ __global__ __launch_bounds__(kBlock) void k_label_core_cells(
 // ALLMUT (all_mutual grids, local run): every candidate cell with core points is mutual and key_of
 //                 (ccmin) is not written -- the core flag core_of[j] stands for key_of[j] >= 0, the
 //                 non-mutual search and the mutual[] loads compile out.
-template <int D, bool GLOBAL, int W = 64, bool ALLMUT = false>
+// XY: float2 points (ALLMUT grids only); the window comes from the key's slab.
+template <int D, bool GLOBAL, int W = 64, bool ALLMUT = false, bool XY = false>
 // 6 waves/SIMD (80 VGPRs, no spill; with two candidate points per lane per round 7 spilled 8)
 // W = 32: two points per wave, one per half (the same candidate loads per point, twice the
 // points in flight: the pass is a chain of dependent loads per point, not bandwidth)
-__global__ __launch_bounds__(kBlock, 6) void k_label(const float4* __restrict__ pts,
+__global__ __launch_bounds__(kBlock, 6) void k_label(const Pt<XY>* __restrict__ pts,
                                                  const int32_t* __restrict__ skey, Geom g,
                                                  const CellRec<D>* __restrict__ crec,
                                                  const uint32_t* __restrict__ occ_bits,
@@ -3621,6 +3714,7 @@ __global__ __launch_bounds__(kBlock, 6) void k_label(const float4* __restrict__ 
                                                  int32_t* __restrict__ kstat = nullptr,
                                                  const uint8_t* __restrict__ core_of = nullptr) {
   static_assert(!ALLMUT || (D == 2 && !GLOBAL), "all-mutual grids are 2-D, local runs");
+  static_assert(!XY || ALLMUT, "xy points only on all-mutual grids");
   // kstat (A/B build, RPT_STATS): queued points, points with a core cell in their window, points
   // that searched a partly reachable cell, points labelled
   static_assert(W == 32 || W == 64, "a point per wave or per half-wave");
@@ -3653,10 +3747,11 @@ __global__ __launch_bounds__(kBlock, 6) void k_label(const float4* __restrict__ 
     bool st_core = false, st_search = false;
 #endif
     if ((int64_t)key < g.cells) {
-      const float4 p = pts[s];
+      const float4 p = load_pt<XY>(pts, s);
       int cx, cy, cz;
       decode_key<D>(key, g, cx, cy, cz);
-      const Window w = make_window<D, false>(cx, cy, cz, p.w, p.w, g, slab_t);
+      const Window w = XY ? slab_window<D>(cx, cy, cz, g.slab_of_key(key), g)
+                          : make_window<D, false>(cx, cy, cz, p.w, p.w, g, slab_t);
       // super-rounds of kR candidates per lane, loads of one kind issued together: the cells'
       // smallest keys (empty cells hold INT_MAX, so no occupancy lookup), then the records of
       // the cells with core points -- two dependent rounds per super-round
@@ -3679,7 +3774,7 @@ __global__ __launch_bounds__(kBlock, 6) void k_label(const float4* __restrict__ 
             cb[k] = cr.b;
             ce[k] = cr.e;
             mu[k] = ALLMUT ? 1 : mutual[c[k]];
-            cls[k] = classify<D>(p, rec_boxA<D>(cr), rec_boxB(cr), g);
+            cls[k] = classify<D, XY>(p, rec_boxA<D>(cr), rec_boxB(cr), g);
             if (cls[k] == 1) v = min(v, ck[k]);
           }
         }
@@ -3737,9 +3832,10 @@ __global__ __launch_bounds__(kBlock, 6) void k_label(const float4* __restrict__ 
                 k1 = v1 ? key_of[j] : -1;
                 k2 = v2 ? key_of[j2] : -1;
               }
-              const float4 p1 = v1 ? pts[j] : p, p2 = v2 ? pts[j2] : p;
-              hit = gbal((k1 >= 0 && adjacent<D>(p, p1, g)) ||
-                         (k2 >= 0 && adjacent<D>(p, p2, g))) != 0;
+              const float4 p1 = v1 ? load_pt<XY>(pts, j) : p;
+              const float4 p2 = v2 ? load_pt<XY>(pts, j2) : p;
+              hit = gbal((k1 >= 0 && adjacent<D, XY>(p, p1, g)) ||
+                         (k2 >= 0 && adjacent<D, XY>(p, p2, g))) != 0;
             }
             if (hit) best = mm;
           } else {
@@ -3748,9 +3844,10 @@ __global__ __launch_bounds__(kBlock, 6) void k_label(const float4* __restrict__ 
               const int j = j0 + hl, j2 = j + W;
               const bool v1 = j < el, v2 = j2 < el;
               const int m1 = v1 ? key_of[j] : -1, m2 = v2 ? key_of[j2] : -1;
-              const float4 p1 = v1 ? pts[j] : p, p2 = v2 ? pts[j2] : p;
-              if (m1 >= 0 && m1 < best && m1 < lb && adjacent<D>(p, p1, g)) lb = m1;
-              if (m2 >= 0 && m2 < best && m2 < lb && adjacent<D>(p, p2, g)) lb = m2;
+              const float4 p1 = v1 ? load_pt<XY>(pts, j) : p;
+              const float4 p2 = v2 ? load_pt<XY>(pts, j2) : p;
+              if (m1 >= 0 && m1 < best && m1 < lb && adjacent<D, XY>(p, p1, g)) lb = m1;
+              if (m2 >= 0 && m2 < best && m2 < lb && adjacent<D, XY>(p, p2, g)) lb = m2;
             }
             best = min(best, gmin(lb));
           }
@@ -4463,6 +4560,62 @@ struct DbscanState {
   // fused local path with a readback of the cluster count; set by union_pass, read by
   // labels_local)
   bool cell_comp = false;
+  // the union passes' A/B switches (read once)
+  void union_env() {
+    if (union_list < 0) {
+      const char* e = ab_env("RPT_UNION_LIST");
+      union_list = (e && std::atoi(e) == 0) ? 0 : 1;
+    }
+    if (union_pair < 0) {
+      const char* e = ab_env("RPT_UNION_PAIR");
+      union_pair = (e && std::atoi(e) == 0) ? 0 : 1;
+    }
+    if (union_nm < 0) {
+      const char* e = ab_env("RPT_UNION_NM");
+      union_nm = (e && std::atoi(e) == 0) ? 0 : 1;
+    }
+    if (uf_compress < 0) {
+      const char* e = ab_env("RPT_UF_COMPRESS");
+      uf_compress = (e && std::atoi(e) == 1) ? 1 : 0;
+    }
+  }
+  // a fused local run on this grid takes the per-cell path (cell_comp; see union_pass)
+  bool cell_comp_ok() {
+    union_env();
+    return all_mutual && dim == 2 && union_list && union_pair && union_nm &&
+           cell_comp_enabled() && !use_label_tiles() && !uf_compress;
+  }
+  // The sorted points are float2 {x, y} in the first half of pts' allocation (Pt<true>), not
+  // float4: the build's writer was k_slab_bucket<true> / k_slab_chunk_scatter<true>.  A kernel
+  // that assumed the other layout would read out of bounds, so the one rule is xy_rule() and
+  // every pass that reads points through a float4 kernel refuses such a state (need_float4).
+  bool xy_points = false;
+  // set by the fused local drivers right before build(), consumed by it: the caller reads the
+  // points only through core_pass / union_pass(fused) / labels_local
+  bool may_xy = false;
+  // Does every point-reading kernel the fused local run will launch on this grid know the xy
+  // layout?  Those are k_cell_box / k_cell_box_mixed, k_core_slow_masked, k_union_listed and
+  // k_label<2, false, 32, true> (k_union_cells_pair reads no point; the per-cell path launches
+  // neither k_union_nm nor a compression pass).  Anything else turns the layout off: the other
+  // K5 pipelines (RPT_K5_MODE / _TILES / _FUSED / _MASK, eps_t >= 3), the per-point union paths
+  // (RPT_UNION_PAIR / _LIST / _NM, RPT_CELL_COMP=0, RPT_UF_COMPRESS=1), the label tiles and the
+  // 64-lane label pass (RPT_K7_TILES, RPT_K7_W=64).  RPT_XY_POINTS=0 keeps float4 (A/B).
+  bool xy_rule() {
+    static const bool on = [] {
+      const char* e = ab_env("RPT_XY_POINTS");
+      return !(e && std::atoi(e) == 0);
+    }();
+    (void)use_label_tiles();  // (reads RPT_K7_TILES)
+    // (a fractional eps_t also keeps float4: its windows are tfree all the same, it is only
+    // not among the cases the layout was measured and tested on)
+    return on && dim == 2 && g.tfree && g.epst == std::floor(g.epst) && cell_comp_ok() &&
+           k5_fused_path() && (int)slab_reach() <= 2 && k5_mask() && !k7_tiles && label_w() == 32;
+  }
+  int32_t need_float4(const char* who) const {
+    if (!xy_points) return RPT_OK;
+    set_error("%s: internal: this state's sorted points are xy-only", who);
+    return RPT_EHIP;
+  }
   int64_t* stmp = nullptr;
   Timer tm;
 
@@ -4681,6 +4834,9 @@ int32_t DbscanState::build_t(const float* x, const float* y, const float* z, int
   bucket_allmin = false;
   const bool bucket = bucket_mode && D == 2 && hb.n_finite_t == n && !hb.t_descends &&
                       (int64_t)nx * ny <= kBucketCells && nt < (int64_t(1) << 31);
+  // xy points: written by the slab writers only, every time finite (no isolated cell)
+  xy_points = may_xy && bucket && D == 2 && hb.n_finite_t == n && xy_rule();
+  Pt<true>* pts_xy = reinterpret_cast<Pt<true>*>(pts);  // the allocation's first half
   if (bucket) {
     hipLaunchKernelGGL(k_slab_lo, dim3(grid_for(64 * (nt + 1), kBlock, 4096)), dim3(kBlock), 0,
                        st, t, n, g, slab_lo, occ_bits, (int64_t)(C1 / 32 + 2));
@@ -4713,7 +4869,8 @@ int32_t DbscanState::build_t(const float* x, const float* y, const float* z, int
       // split to fill the GPU) keep the one-block-per-slab scan (125 frames: 38 vs 53 us)
       RPT_HIP(hipFuncSetAttribute((const void*)k_slab_chunk_hist,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_bytes));
-      RPT_HIP(hipFuncSetAttribute((const void*)k_slab_chunk_scatter,
+      RPT_HIP(hipFuncSetAttribute(xy_points ? (const void*)k_slab_chunk_scatter<true>
+                                            : (const void*)k_slab_chunk_scatter<false>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_bytes));
       hipLaunchKernelGGL(k_slab_chunk_hist, dim3((unsigned)(nt * CH)), dim3(kBucketBlock),
                          hist_bytes, st, x, y, stride, g, slab_lo, CH, hist_g);
@@ -4739,30 +4896,45 @@ int32_t DbscanState::build_t(const float* x, const float* y, const float* z, int
                            st, cell_root, P, nt, occ_base);
         RPT_CHECK_LAUNCH();
       }
-      hipLaunchKernelGGL(k_slab_chunk_scatter, dim3((unsigned)(nt * CH)), dim3(kBucketBlock),
-                         hist_bytes, st, x, y, stride, t, g, slab_lo, CH, hist_g, pts, sorig,
-                         skey, spos_w);
+      if (xy_points)
+        hipLaunchKernelGGL(k_slab_chunk_scatter<true>, dim3((unsigned)(nt * CH)),
+                           dim3(kBucketBlock), hist_bytes, st, x, y, stride, t, g, slab_lo, CH,
+                           hist_g, pts_xy, sorig, skey, spos_w, slab_t);
+      else
+        hipLaunchKernelGGL(k_slab_chunk_scatter<false>, dim3((unsigned)(nt * CH)),
+                           dim3(kBucketBlock), hist_bytes, st, x, y, stride, t, g, slab_lo, CH,
+                           hist_g, pts, sorig, skey, spos_w, (float2*)nullptr);
     } else {
       // the fused K5's all-core cell minima from the counting sort when both LDS arrays fit 64 KiB
       bucket_allmin = k5_fused_path() && 2 * hist_bytes <= 65536 &&
                       ab_mode("RPT_BUCKET_ALLMIN") != 0;  // (=0: from k_cell_box; A/B)
       const size_t lds = bucket_allmin ? 2 * hist_bytes : hist_bytes;
-      RPT_HIP(hipFuncSetAttribute((const void*)k_slab_bucket,
+      RPT_HIP(hipFuncSetAttribute(xy_points ? (const void*)k_slab_bucket<true>
+                                            : (const void*)k_slab_bucket<false>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 #ifdef RPT_AB
       if (ab_env("RPT_STATS")) {  // A/B diagnostics: blocks per CU the runtime admits
         int nb = -1;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_slab_bucket, kBucketBlock, lds);
+        if (xy_points)
+          (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_slab_bucket<true>,
+                                                             kBucketBlock, lds);
+        else
+          (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_slab_bucket<false>,
+                                                             kBucketBlock, lds);
         std::fprintf(stderr, "[rpt stats] slab_bucket lds=%zu nx=%d ny=%d blocks_per_cu=%d\n", lds,
                      (int)nx, (int)ny, nb);
       }
 #endif
-      hipLaunchKernelGGL(k_slab_bucket, dim3((unsigned)nt), dim3(kBucketBlock), lds, st, x, y,
-                         stride, t, g, slab_lo, pts, sorig, skey, spos_w, cell_start, hpos,
-                         slab_occ,
-                         occ_bits,
-                         bucket_allmin ? reinterpret_cast<unsigned long long*>(cell_min_pair)
-                                       : nullptr);
+      auto* cmin_all =
+          bucket_allmin ? reinterpret_cast<unsigned long long*>(cell_min_pair) : nullptr;
+      if (xy_points)
+        hipLaunchKernelGGL(k_slab_bucket<true>, dim3((unsigned)nt), dim3(kBucketBlock), lds, st,
+                           x, y, stride, t, g, slab_lo, pts_xy, sorig, skey, spos_w, cell_start,
+                           hpos, slab_occ, occ_bits, cmin_all, slab_t);
+      else
+        hipLaunchKernelGGL(k_slab_bucket<false>, dim3((unsigned)nt), dim3(kBucketBlock), lds, st,
+                           x, y, stride, t, g, slab_lo, pts, sorig, skey, spos_w, cell_start,
+                           hpos, slab_occ, occ_bits, cmin_all, (float2*)nullptr);
     }
     RPT_CHECK_LAUNCH();
     if (coalesced_scan) {
@@ -4803,17 +4975,31 @@ int32_t DbscanState::build_t(const float* x, const float* y, const float* z, int
     // the 125-frame share has too few 64-cell waves to fill the GPU (48 -> 60 us) and dense
     // slabs' cells are large (324 -> 402 us): 16 lanes for every cell there
     // (RPT_CELL_BOX_MIXED=0 in the A/B build: always)
-    if (cell_box_mixed() == 2 ||
-        (cell_box_mixed() == 1 && !dense_slabs && n > (int64_t(1) << 24)))
-      hipLaunchKernelGGL(k_cell_box_mixed<D>, dim3(grid_for(n, kBlock, 4096)), dim3(kBlock), 0, st,
-                         pts, cell_start, occ, n_occ_dev, g, mutual, cr, cmin_w, so_w);
+    const bool mixed = cell_box_mixed() == 2 ||
+                       (cell_box_mixed() == 1 && !dense_slabs && n > (int64_t(1) << 24));
+    const dim3 gm(grid_for(n, kBlock, 4096)), gl(grid_for(kCbLanes * n, kBlock, 8192));
+    if (xy_points) {
+      if constexpr (D == 2) {  // (the records' time fields from slab_t, written above)
+        if (mixed)
+          hipLaunchKernelGGL((k_cell_box_mixed<2, true>), gm, dim3(kBlock), 0, st, pts_xy,
+                             cell_start, occ, n_occ_dev, g, mutual, cr, cmin_w, so_w, slab_t);
+        else
+          hipLaunchKernelGGL((k_cell_box<2, true>), gl, dim3(kBlock), 0, st, pts_xy, cell_start,
+                             occ, n_occ_dev, g, mutual, cr, cmin_w, so_w, slab_t);
+      }
+    } else if (mixed)
+      hipLaunchKernelGGL(k_cell_box_mixed<D>, gm, dim3(kBlock), 0, st, pts, cell_start, occ,
+                         n_occ_dev, g, mutual, cr, cmin_w, so_w);
     else
-      hipLaunchKernelGGL(k_cell_box<D>, dim3(grid_for(kCbLanes * n, kBlock, 8192)), dim3(kBlock),
-                         0, st, pts, cell_start, occ, n_occ_dev, g, mutual, cr, cmin_w, so_w);
+      hipLaunchKernelGGL(k_cell_box<D>, gl, dim3(kBlock), 0, st, pts, cell_start, occ, n_occ_dev,
+                         g, mutual, cr, cmin_w, so_w);
   }
   RPT_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_slab_range<D>, dim3((unsigned)nt), dim3(kBlock), 0, st, cr, occ, hpos,
-                     cell_start, (int64_t)(C / nt), (int)nt, slab_t, bucket ? occ_base : nullptr);
+  // (xy points: the writer filled slab_t from the slabs' own time values)
+  if (!xy_points)
+    hipLaunchKernelGGL(k_slab_range<D>, dim3((unsigned)nt), dim3(kBlock), 0, st, cr, occ, hpos,
+                       cell_start, (int64_t)(C / nt), (int)nt, slab_t,
+                       bucket ? occ_base : nullptr);
   RPT_CHECK_LAUNCH();
   tm.mark();
   return RPT_OK;
@@ -4825,6 +5011,11 @@ int32_t DbscanState::build(const float* x, const float* y, const float* z, int64
   n = n_;
   dim = z ? 3 : 2;
   min_samples = ms;
+  xy_points = false;
+  struct Consume {  // the caller's promise covers this build only
+    bool& f;
+    ~Consume() { f = false; }
+  } consume{may_xy};
   tm.start(timing, st);
   degenerate = !(eps_space >= 0.0) || !((float)eps_time >= 0.0f);
   if (degenerate) return RPT_OK;
@@ -4846,6 +5037,7 @@ int32_t DbscanState::core_pass(hipStream_t st) {
   k5_env();
   const double rs = slab_reach();
   const bool oct = oct_ok();
+  if (!k5_fused_path()) RPT_TRY(need_float4("core_pass"));
 #ifdef RPT_AB  // A/B-only forms (stdbscan_ab.inc)
   if (oct && k5_tiles) {
     // LDS tiles: band height BY with the map (W slabs x BY + 4 rows x nx) and the undecided list
@@ -4915,6 +5107,7 @@ int32_t DbscanState::core_pass(hipStream_t st) {
     // x 5 columns fit a 128-bit mask (W <= 5; pmask / clo per occupied cell in the dead radix
     // buffers / cid, both rebuilt later)
     const bool masked = (int)rs <= 2 && k5_mask();
+    if (!masked) RPT_TRY(need_float4("core_pass"));
     uint4* k5m = reinterpret_cast<uint4*>(pmask);
     if (masked) {
       hipLaunchKernelGGL((k_core_cells_oct<true, true>),
@@ -4922,8 +5115,14 @@ int32_t DbscanState::core_pass(hipStream_t st) {
                          (int)rs, occ, n_occ, rec<2>(), mutual, occ_bits, slab_t,
                          (int32_t*)nullptr, (int32_t*)nullptr, core, cm, slow, cq, n_slow, k5m,
                          cid);
-      hipLaunchKernelGGL(k_core_slow_masked, dim3(wave_grid(n)), dim3(kBlock), 0, st, pts, g,
-                         (int)rs, rec<2>(), occ, slow, cq, n_slow, k5m, cid, core, sorig, cm);
+      if (xy_points)
+        hipLaunchKernelGGL(k_core_slow_masked<true>, dim3(wave_grid(n)), dim3(kBlock), 0, st,
+                           reinterpret_cast<const Pt<true>*>(pts), g, (int)rs, rec<2>(), occ,
+                           slow, cq, n_slow, k5m, cid, core, sorig, cm);
+      else
+        hipLaunchKernelGGL(k_core_slow_masked<false>, dim3(wave_grid(n)), dim3(kBlock), 0, st,
+                           pts, g, (int)rs, rec<2>(), occ, slow, cq, n_slow, k5m, cid, core,
+                           sorig, cm);
     } else {
       hipLaunchKernelGGL(k_core_cells_oct<true>, dim3((grid_for(8 * n, kBlock, 8192) + 7) & ~7),
                          dim3(kBlock), 0, st, g, (int)rs, occ, n_occ, rec<2>(), mutual, occ_bits,
@@ -5005,14 +5204,7 @@ int32_t DbscanState::union_pass(hipStream_t st, bool fused) {
   (void)gc;
   // per-cell (min original index, sorted index) of the core points, one u64 per cell
   auto* cmin = reinterpret_cast<unsigned long long*>(cell_min_pair);
-  if (union_list < 0) {
-    const char* e = ab_env("RPT_UNION_LIST");
-    union_list = (e && std::atoi(e) == 0) ? 0 : 1;
-  }
-  if (union_pair < 0) {
-    const char* e = ab_env("RPT_UNION_PAIR");
-    union_pair = (e && std::atoi(e) == 0) ? 0 : 1;
-  }
+  union_env();
   // 2-D: the first union pass lists its cells with undecided candidates in nc_list (free until
   // the label pass), their count at nc_list[n] (zeroed by k_init_occ_cells)
   const bool listing = union_list && dim == 2;
@@ -5021,10 +5213,6 @@ int32_t DbscanState::union_pass(hipStream_t st, bool fused) {
   // 2-D pair path: the non-mutual cells with core points listed by the first pass in cid (free
   // until the label pass), their count at cid[n]; k_union_nm then takes only their points
   // (RPT_UNION_NM=0 in the A/B build: k_union over every point)
-  if (union_nm < 0) {
-    const char* e = ab_env("RPT_UNION_NM");
-    union_nm = (e && std::atoi(e) == 0) ? 0 : 1;
-  }
   const bool nm = dim == 2 && union_pair && union_nm;
   int32_t* nm_list = nm ? cid : nullptr;
   int32_t* nm_count = nm ? cid + n : nullptr;
@@ -5034,12 +5222,9 @@ int32_t DbscanState::union_pass(hipStream_t st, bool fused) {
   // cells, has nothing listed and is not launched), so the star initialisation is per cell
   // (not with the A/B label tiles, which read ccmin, nor with the A/B compression pass:
   // k_compress walks EVERY core point's parent chain, so it keeps the per-point init)
-  if (uf_compress < 0) {
-    const char* e = ab_env("RPT_UF_COMPRESS");
-    uf_compress = (e && std::atoi(e) == 1) ? 1 : 0;
-  }
-  cell_comp = fused && all_mutual && listing && nm && cell_comp_enabled() && !use_label_tiles() &&
-              !uf_compress;
+  cell_comp = fused && cell_comp_ok();
+  // (xy points: only the per-cell path's kernels below know the layout)
+  if (!cell_comp) RPT_TRY(need_float4("union_pass"));
   // the per-cell minima: from the core pass (cmin_ready) or from the final core flags here
   if (!cell_comp || !cmin_ready)
     hipLaunchKernelGGL(k_init_occ_cells, dim3(gb), dim3(kBlock), 0, st, occ, n_occ, C, rep,
@@ -5080,9 +5265,16 @@ int32_t DbscanState::union_pass(hipStream_t st, bool fused) {
       if (snap)
         hipLaunchKernelGGL(k_cell_root_snapshot, dim3(grid_for(n, kBlock, 4096)), dim3(kBlock),
                            0, st, occ, n_occ, rep, parent, g.cells, uf_flags, cell_root);
-      hipLaunchKernelGGL(k_union_listed, dim3(gw), dim3(kBlock), 0, st, pts, g, occ, rec<2>(),
-                         occ_bits, slab_t, core, rep, mutual, sorig, parent, uf_flags, pm, plist,
-                         pcount, snap ? (const int32_t*)cell_root : nullptr, lstat_dev);
+      const int32_t* croot = snap ? (const int32_t*)cell_root : nullptr;
+      if (xy_points)
+        hipLaunchKernelGGL(k_union_listed<true>, dim3(gw), dim3(kBlock), 0, st,
+                           reinterpret_cast<const Pt<true>*>(pts), g, occ, rec<2>(), occ_bits,
+                           slab_t, core, rep, mutual, sorig, parent, uf_flags, pm, plist, pcount,
+                           croot, lstat_dev);
+      else
+        hipLaunchKernelGGL(k_union_listed<false>, dim3(gw), dim3(kBlock), 0, st, pts, g, occ,
+                           rec<2>(), occ_bits, slab_t, core, rep, mutual, sorig, parent, uf_flags,
+                           pm, plist, pcount, croot, lstat_dev);
     }
     else
       hipLaunchKernelGGL((k_union_cells<2, true>), dim3(gw), dim3(kBlock), 0, st, pts, g,
@@ -5125,8 +5317,8 @@ int32_t DbscanState::union_pass(hipStream_t st, bool fused) {
                  "roots_differ=%d searches=%d hits=%d\n",
                  (long long)n, h[0], h[1], ls[0], ls[1], ls[2], ls[3]);
     // the union init / component / core-label path of this run
-    std::fprintf(stderr, "[rpt stats] n=%lld all_mutual=%d cell_comp=%d\n", (long long)n,
-                 all_mutual ? 1 : 0, cell_comp ? 1 : 0);
+    std::fprintf(stderr, "[rpt stats] n=%lld all_mutual=%d cell_comp=%d xy_points=%d\n",
+                 (long long)n, all_mutual ? 1 : 0, cell_comp ? 1 : 0, xy_points ? 1 : 0);
   }
 #endif
   RPT_CHECK_LAUNCH();
@@ -5207,6 +5399,7 @@ int32_t DbscanState::labels_local(int32_t* labels, rpt_stdbscan_stats* stats, hi
       hipLaunchKernelGGL(k_label_core, dim3(glc), dim3(kBlock), 0, st, ccmin, n, sorig, mr,
                          labels);
   }
+  if (!cell_comp || label_w() != 32 || use_label_tiles()) RPT_TRY(need_float4("labels_local"));
   int32_t* kstat = nullptr;  // (A/B diagnostics)
 #ifdef RPT_AB
   if (ab_env("RPT_STATS")) {  // (a leaked 16 B per process)
@@ -5233,7 +5426,12 @@ int32_t DbscanState::labels_local(int32_t* labels, rpt_stdbscan_stats* stats, hi
                        nc_list, nc_count, labels);
   else
 #endif
-  if (cell_comp)
+  if (cell_comp && xy_points)
+    hipLaunchKernelGGL((k_label<2, false, 32, true, true>), dim3(wave_grid(n)), dim3(kBlock), 0,
+                       st, reinterpret_cast<const Pt<true>*>(pts), skey, g, rec<2>(), occ_bits,
+                       slab_t, (const int32_t*)nullptr, cell_min, mutual, sorig, mr, nc_list,
+                       nc_count, labels, kstat, core);
+  else if (cell_comp)
     hipLaunchKernelGGL((k_label<2, false, 32, true>), dim3(wave_grid(n)), dim3(kBlock), 0, st,
                        pts, skey, g, rec<2>(), occ_bits, slab_t, (const int32_t*)nullptr,
                        cell_min, mutual, sorig, mr, nc_list, nc_count, labels, kstat, core);
@@ -5301,6 +5499,7 @@ int32_t DbscanState::labels_global(const int64_t* rep_orig, const int64_t* reps,
     set_error("rpt_dbscan_labels_global: degenerate parameters are handled by rpt_stdbscan");
     return RPT_ENOTSUP;
   }
+  RPT_TRY(need_float4("labels_global"));
   const int gb = grid_for(n, kBlock, 2048);
   int32_t* nc_count = nc_list + n;
   const bool cr = cell_roots_enabled();
@@ -5357,6 +5556,7 @@ int32_t DbscanState::labels_global(const int64_t* rep_orig, const int64_t* reps,
 
 int32_t DbscanState::frames_pass(int32_t min_frames, hipStream_t st) {
   if (degenerate || min_frames < 1) return RPT_OK;  // <= 0: every core point qualifies
+  RPT_TRY(need_float4("frames_pass"));
   cmin_ready = false;  // core points may be demoted below
   const bool refine = min_frames >= 2;
   int32_t* list = nc_list;  // free until labels_fifo rebuilds it
@@ -5401,6 +5601,7 @@ int32_t DbscanState::frames_pass(int32_t min_frames, hipStream_t st) {
 }
 
 int32_t DbscanState::labels_fifo(int32_t* labels, rpt_stdbscan_stats* stats, hipStream_t st) {
+  RPT_TRY(need_float4("labels_fifo"));
   int32_t* nc_count = nc_list + n;  // k_ccmin's non-core queue counter, cleared by cluster_ids
   int32_t* spos = slab;
   RPT_TRY(cluster_ids(st, nullptr, nc_count));
@@ -5470,6 +5671,7 @@ int32_t stdbscan(const float* x, const float* y, const float* z, int64_t stride,
       g_states.push_back({{dev, st}, S});
     }
   }
+  S->may_xy = stats != nullptr;  // (with stats: union_pass runs fused)
   RPT_TRY(S->build(x, y, z, stride, t, n, eps_space, eps_time, min_samples,
                    stats && stats->timing, st));
   RPT_TRY(S->core_pass(st));
@@ -5587,6 +5789,7 @@ int32_t stdbscan_deferred(const float* x, const float* y, const float* z, int64_
     }
   }
   S->given_bounds = host_bounds;
+  S->may_xy = true;
   const int32_t sb = S->build(x, y, z, stride, t, n, eps_space, eps_time, min_samples,
                               stats->timing != 0, st);
   S->given_bounds = nullptr;
