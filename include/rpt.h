@@ -26,6 +26,8 @@
  *   rpt_shard_*                      the same stages over a frame range of a multi-GPU stack
  *   rpt_fuse_gains_max               fuse_gains_max PointCloudWork/5_gain_fusion_ply_builder.py:222-273
  *   rpt_csv_*                        pd.read_csv + fillna/to_numpy of load_radar_csv :189-211
+ *   rpt_text_rows_size /             the per-point f-string of write_ply radar_pipeline/core/writers.py:45-46
+ *   rpt_text_rows_write              and np.savetxt(fmt="%.6f,%.6f,%.6f,%d") of write_labels_csv :79-81
  *   rpt_synth_echo                   (bench/test input generator; no reference counterpart)
  */
 #ifndef RPT_H
@@ -236,6 +238,29 @@ int32_t rpt_infer_time_from_colors(const uint8_t* colors, int64_t n, const float
 int32_t rpt_fuse_gains_max(const float* x, const float* y, const float* intensity, int64_t n,
                            double grid_resolution, double* out_x, double* out_y,
                            float* out_intensity, int64_t* n_out_host, void* stream);
+
+/* ---- "%.6f" text rows (the PLY vertex lines and the labels CSV) --------------------------
+ * Row i of a layout, formatted on the device byte for byte as CPython formats it:
+ *   RPT_TEXT_PLY     "%.6f %.6f %.6f %d %d %d\n"  x, y, z f32 [n], tail = rgb u8 [n][3]
+ *   RPT_TEXT_LABELS  "%.6f,%.6f,%.6f,%d\n"        x, y, z f32 [n], tail = label i32 [n]
+ * "%.6f" is the exact decimal expansion of the float32 value rounded half to even at the sixth
+ * decimal ("%.6f" % float(np.float32(v))), computed in integers; -0.0 and negatives that round to
+ * zero print "-0.000000".  Domain: finite values with |v| < 2^40.  A row holding any other value
+ * (NaN, inf, larger) gets length 0 and is counted in *n_unsupported_host: a caller that sees a
+ * non-zero count formats the file on the host instead.
+ * rpt_text_rows_size: row_offsets (dev int64 [n+1]) = exclusive scan of the row lengths with the
+ * total at [n]; *total_host and *n_unsupported_host are read back (synchronises).
+ * rpt_text_rows_write: the rows at out + row_offsets[i] (out dev u8 [out_bytes], out_bytes >=
+ * the total).  The inputs must be those given to rpt_text_rows_size; a row whose length does not
+ * match its offsets, and a block of rows whose range does not lie inside [0, out_bytes), are
+ * skipped -- nothing is written outside out whatever the inputs hold.  No sync. */
+enum { RPT_TEXT_PLY = 0, RPT_TEXT_LABELS = 1 };
+int32_t rpt_text_rows_size(int32_t layout, const float* x, const float* y, const float* z,
+                           const void* tail, int64_t n, int64_t* row_offsets /*dev [n+1]*/,
+                           int64_t* total_host, int64_t* n_unsupported_host, void* stream);
+int32_t rpt_text_rows_write(int32_t layout, const float* x, const float* y, const float* z,
+                            const void* tail, int64_t n, const int64_t* row_offsets /*dev*/,
+                            uint8_t* out /*dev [out_bytes]*/, int64_t out_bytes, void* stream);
 
 /* ---- K9: per-(frame, label) cluster summaries ---------------------------------------
  * point_frame[n] (dev, i32, non-decreasing frame slot per point), labels[n] from

@@ -74,6 +74,12 @@ int32_t remap_components(const int32_t* comp, int64_t n, int64_t base, const int
                          const int64_t* vals, int64_t nk, int64_t* out, hipStream_t st);
 int32_t select_roots(const int64_t* rep, int64_t base, int64_t lo, int64_t hi, int64_t* out,
                      int64_t* count_host, hipStream_t st);
+int32_t text_rows_size(int32_t layout, const float* x, const float* y, const float* z,
+                       const void* tail, int64_t n, int64_t* row_offsets, int64_t* total_host,
+                       int64_t* n_bad_host, hipStream_t st);
+int32_t text_rows_write(int32_t layout, const float* x, const float* y, const float* z,
+                        const void* tail, int64_t n, const int64_t* row_offsets, uint8_t* out,
+                        int64_t out_bytes, hipStream_t st);
 }  // namespace rpt
 
 struct rpt_dbscan {
@@ -321,6 +327,40 @@ int32_t rpt_infer_time_from_colors(const uint8_t* colors, int64_t n, const float
   rpt::clear_error();
   return rpt::infer_time_from_colors(colors, n, palette, n_pal, times_out,
                                      rpt::as_stream(stream));
+}
+
+int32_t rpt_text_rows_size(int32_t layout, const float* x, const float* y, const float* z,
+                           const void* tail, int64_t n, int64_t* row_offsets,
+                           int64_t* total_host, int64_t* n_unsupported_host, void* stream) {
+  rpt::clear_error();
+  if ((layout != RPT_TEXT_PLY && layout != RPT_TEXT_LABELS) || n < 0 || !row_offsets ||
+      !total_host || !n_unsupported_host || (n > 0 && (!x || !y || !z || !tail))) {
+    rpt::set_error("rpt_text_rows_size: bad arguments");
+    return RPT_EINVAL;
+  }
+  if (n >= (int64_t(1) << 39)) {  // one block per 256 rows in a 31-bit grid
+    rpt::set_error("rpt_text_rows_size: n=%lld rows exceed the launch grid", (long long)n);
+    return RPT_ENOTSUP;
+  }
+  return rpt::text_rows_size(layout, x, y, z, tail, n, row_offsets, total_host,
+                             n_unsupported_host, rpt::as_stream(stream));
+}
+
+int32_t rpt_text_rows_write(int32_t layout, const float* x, const float* y, const float* z,
+                            const void* tail, int64_t n, const int64_t* row_offsets,
+                            uint8_t* out, int64_t out_bytes, void* stream) {
+  rpt::clear_error();
+  if ((layout != RPT_TEXT_PLY && layout != RPT_TEXT_LABELS) || n < 0 || out_bytes < 0 ||
+      (n > 0 && (!x || !y || !z || !tail || !row_offsets || (out_bytes > 0 && !out)))) {
+    rpt::set_error("rpt_text_rows_write: bad arguments");
+    return RPT_EINVAL;
+  }
+  if (n >= (int64_t(1) << 39)) {
+    rpt::set_error("rpt_text_rows_write: n=%lld rows exceed the launch grid", (long long)n);
+    return RPT_ENOTSUP;
+  }
+  return rpt::text_rows_write(layout, x, y, z, tail, n, row_offsets, out, out_bytes,
+                              rpt::as_stream(stream));
 }
 
 int32_t rpt_cluster_summaries(const int32_t* labels, const float* x, const float* y,

@@ -22,6 +22,9 @@ RPT_ENONFINITE = 6
 ECHO_F32 = 0
 ECHO_U8 = 1
 
+TEXT_PLY = 0
+TEXT_LABELS = 1
+
 c_f32p = C.POINTER(C.c_float)
 c_f64p = C.POINTER(C.c_double)
 c_i32p = C.POINTER(C.c_int32)
@@ -247,6 +250,10 @@ _SIGS = [
                                                 c_f64p]),
     ("rpt_fuse_gains_max", C.c_int32,
      [vp, vp, vp, C.c_int64, C.c_double, vp, vp, vp, c_i64p, vp]),
+    ("rpt_text_rows_size", C.c_int32,
+     [C.c_int32, vp, vp, vp, vp, C.c_int64, vp, c_i64p, c_i64p, vp]),
+    ("rpt_text_rows_write", C.c_int32,
+     [C.c_int32, vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int64, vp]),
     ("rpt_csv_count_rows", C.c_int32, [C.POINTER(C.c_char_p), C.c_int32, c_i64p, C.c_int32]),
     ("rpt_csv_parse_sweeps", C.c_int32,
      [C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, c_f32p, c_f32p,

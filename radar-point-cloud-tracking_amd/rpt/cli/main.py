@@ -1,8 +1,9 @@
-"""Drop-in for the ``radar-pipeline`` click group's ``cluster`` command
-(radar-pipeline/src/radar_pipeline/cli/main.py:17-35, 188-253): the same group options
-(-c/--config YAML, -v, --version) and the same cluster arguments, with ST-DBSCAN on the MI355X.
-The file-management commands of the group (sort-by-gain, filter-range, convert, build,
-visualize) and the --plot PNG are outside this engine's scope."""
+"""Drop-in for the ``radar-pipeline`` click group's ``build`` and ``cluster`` commands
+(radar-pipeline/src/radar_pipeline/cli/main.py:17-35, 117-161, 188-253): the same group options
+(-c/--config YAML, -v, --version) and the same arguments -- sweep CSVs to stacked PLYs to
+ST-DBSCAN labels, with the points, the clustering and the text of both files made on the MI355X.
+The file-management commands of the group (sort-by-gain, filter-range, convert, visualize) and
+the --plot PNGs are outside this engine's scope."""
 from __future__ import annotations
 
 import sys
@@ -26,6 +27,26 @@ def cli(ctx: click.Context, config: Optional[Path], verbose: int) -> None:
     ctx.ensure_object(dict)
     ctx.obj["config"] = PipelineConfig.from_yaml(config) if config else PipelineConfig()
     ctx.obj["verbose"] = verbose
+
+
+@cli.command("build")
+@click.argument("input_dir", type=click.Path(exists=True, path_type=Path))
+@click.argument("output_dir", type=click.Path(path_type=Path))
+@click.option("--flat/--no-flat", default=True, help="Generate flat stack.")
+@click.option("--offset/--no-offset", default=True, help="Generate offset stack.")
+@click.option("--plot/--no-plot", default=True, help="Generate PNG previews.")
+@click.pass_context
+def build(ctx: click.Context, input_dir: Path, output_dir: Path, flat: bool, offset: bool,
+          plot: bool) -> None:
+    """Build stacked PLY point clouds from Cartesian CSVs."""
+    from ..processors.point_cloud import build_stacked_clouds
+
+    config: PipelineConfig = ctx.obj["config"]
+    build_stacked_clouds(input_dir, output_dir, config.processing, config.gains, config.radar,
+                         generate_flat=flat, generate_offset=offset)
+    if plot:
+        click.echo("note: the --plot PNG is not rendered by rpt", err=True)
+    click.echo("Build complete.")
 
 
 @cli.command("cluster")

@@ -39,7 +39,8 @@ class PointCloud:
 
     @property
     def size(self) -> int:
-        return self.x.size
+        numel = getattr(self.x, "numel", None)  # torch members (the build path keeps them there)
+        return numel() if numel is not None else self.x.size
 
     def to_coords(self) -> np.ndarray:
         return np.column_stack((self.x, self.y, self.z))
@@ -78,6 +79,69 @@ def load_radar_csv(path: Path, config: Optional[RadarConfig] = None) -> RadarSwe
         gain = int(float(b.gain[0]))
     return RadarSweep(angles_rad=angles_rad, ranges=ranges, intensities=echo, scale=scale,
                       gain=gain, source_path=path)
+
+
+def _simple_sweep_echo(path: Path) -> np.ndarray:
+    """Columns 5 onward of ``pd.read_csv(path, header=None, skiprows=1)`` through the native
+    parser: the column count is that of the first data line, as read_csv infers it.  Empty echo
+    fields read 0 where pandas reads NaN (neither passes a threshold >= 0)."""
+    from .ingest import STATUS_EMPTY, STATUS_NON_NUMERIC, STATUS_OK, read_sweeps
+
+    path = Path(path)
+    first = None
+    with path.open("r", encoding="utf-8") as fh:  # raises FileNotFoundError as read_csv does
+        fh.readline()
+        for line in fh:
+            if line.strip():
+                first = line
+                break
+    if first is None:
+        raise ValueError("No columns to parse from file")  # pandas.errors.EmptyDataError
+    bins = len(first.rstrip("\r\n").split(",")) - 5
+    if bins < 1:  # no echo column at all: df.iloc[:, 5:] is empty
+        rows = sum(1 for ln in path.read_text(encoding="utf-8").splitlines()[1:] if ln.strip())
+        return np.zeros((rows, 0), np.float32)
+    b = read_sweeps([path], bins=bins)
+    st = int(b.status[0])
+    if st == STATUS_EMPTY:
+        raise ValueError("No columns to parse from file")
+    if st == STATUS_NON_NUMERIC:
+        raise ValueError(b.errors[0] or f"could not convert string to float in {path}")
+    if st != STATUS_OK:
+        raise ValueError(b.errors[0] or f"Error tokenizing data in {path}")
+    echo = b.echo[0, :int(b.rows[0])]
+    return echo if echo.dtype == np.float32 else echo.astype(np.float32)
+
+
+def load_radar_sweep_simple(path: Path) -> tuple[np.ndarray, np.ndarray]:
+    """loaders.py:104-122: (angles_rad, intensities) with the rows spread evenly over the circle
+    (np.linspace(0, 2 pi, rows, endpoint=False, dtype=float32))."""
+    intensities = _simple_sweep_echo(path)
+    angles_rad = np.linspace(0.0, 2 * np.pi, len(intensities), endpoint=False, dtype=np.float32)
+    return angles_rad, intensities
+
+
+def load_cartesian_csv(path: Path) -> PointCloud:
+    """loaders.py:125-146: a CSV with x, y, z columns (any case; else the first three), pandas as
+    the reference."""
+    import pandas as pd
+
+    df = pd.read_csv(path)
+    by_lower = {c.lower(): c for c in df.columns}
+    cols = [by_lower.get(name, df.columns[k]) for k, name in enumerate("xyz")]
+    x, y, z = (df[c].to_numpy(np.float32) for c in cols)
+    return PointCloud(x=x, y=y, z=z)
+
+
+def detect_csv_format(path: Path) -> str:
+    """loaders.py:223-243: "cartesian" for an x/y/z header or three named columns, else "radar"."""
+    import pandas as pd
+
+    preview = pd.read_csv(path, nrows=2)
+    names = [c.lower() for c in preview.columns]
+    if {"x", "y", "z"}.issubset(names) or (preview.shape[1] == 3 and preview.columns[0] != 0):
+        return "cartesian"
+    return "radar"
 
 
 def load_ply(path: Path) -> PointCloud:

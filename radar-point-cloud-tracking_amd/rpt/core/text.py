@@ -1,0 +1,203 @@
+"""``"%.6f"`` text rows: the vertex lines of ``write_ply`` (radar_pipeline/core/writers.py:45-46,
+one f-string per point) and the rows of ``write_labels_csv`` (:79-81, ``np.savetxt``), formed on
+the device by librpt (csrc/text.hip: rpt_text_rows_size / rpt_text_rows_write).
+
+Both writers reduce to CPython's ``"%.6f" % float(np.float32(v))``; the kernel reproduces it in
+integers for finite ``|v| < 2**40``.  Inputs outside that domain (NaN, inf, larger magnitudes),
+inputs of other dtypes and hosts without a GPU take the host formatter below, which evaluates the
+reference expression itself -- same bytes, at CPython's speed.
+
+Torch device tensors in -> a device ``uint8`` tensor out; numpy in -> ``bytes`` out.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+import torch
+
+from .. import _abi
+from .._device import is_torch, stream_handle
+
+_HOST_CHUNK = 1 << 18      # rows per host-formatted piece
+_COPY_CHUNK = 1 << 25      # bytes per pinned staging buffer
+
+
+def gpu_visible() -> bool:
+    """A ROCm device and librpt.so are both there (the device formatter can run)."""
+    return _abi.load(require=False) is not None and torch.cuda.is_available()
+
+
+# ---- host formatter (the reference expressions) ---------------------------------------------
+
+def _np(a) -> np.ndarray:
+    return a.detach().cpu().numpy() if is_torch(a) else np.asarray(a)
+
+
+def format_ply_rows_host(x, y, z, rgb) -> bytes:
+    """``f"{xp:.6f} {yp:.6f} {zp:.6f} {r} {g} {b}\\n"`` per point (writers.py:45-46)."""
+    x, y, z, rgb = _np(x), _np(y), _np(z), _np(rgb)
+    if rgb.dtype.kind not in "iub":  # str() of a float colour is not "%d": the f-string itself
+        return "".join(f"{xp:.6f} {yp:.6f} {zp:.6f} {r} {g} {b}\n"
+                       for xp, yp, zp, (r, g, b) in zip(x, y, z, rgb)).encode()
+    n = min(len(x), len(y), len(z), len(rgb))  # zip(strict=False)
+    parts = []
+    for lo in range(0, n, _HOST_CHUNK):
+        s = slice(lo, min(lo + _HOST_CHUNK, n))
+        c = rgb[s]
+        parts.append("".join(
+            ["%.6f %.6f %.6f %d %d %d\n" % t
+             for t in zip(x[s].tolist(), y[s].tolist(), z[s].tolist(), c[:, 0].tolist(),
+                          c[:, 1].tolist(), c[:, 2].tolist())]))
+    return "".join(parts).encode()
+
+
+def format_label_rows_host(x, y, z, labels) -> bytes:
+    """The data rows of ``np.savetxt(column_stack((coords, labels)), fmt="%.6f,%.6f,%.6f,%d")``
+    (writers.py:79-81): every column promoted to float64, ``%d`` of the label."""
+    cols = [_np(a).astype(np.float64) for a in (x, y, z, labels)]
+    n = len(cols[0])
+    parts = []
+    for lo in range(0, n, _HOST_CHUNK):
+        s = slice(lo, min(lo + _HOST_CHUNK, n))
+        parts.append("".join(["%.6f,%.6f,%.6f,%d\n" % t
+                              for t in zip(*(c[s].tolist() for c in cols))]))
+    return "".join(parts).encode()
+
+
+# ---- device formatter -------------------------------------------------------------------------
+
+def _device_rows(layout: int, x, y, z, tail) -> Optional[torch.Tensor]:
+    """Rows of contiguous device tensors (x, y, z float32 [n]; tail uint8 [n][3] or int32 [n]) as
+    a device uint8 tensor, or None when a row is outside the kernel's domain."""
+    dev = x.device
+    n = x.numel()
+    lib = _abi.load()
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    total = C.c_int64(0)
+    bad = C.c_int64(0)
+    with torch.cuda.device(dev):
+        st = stream_handle(dev)
+        _abi.check(lib.rpt_text_rows_size(layout, x.data_ptr(), y.data_ptr(), z.data_ptr(),
+                                          tail.data_ptr(), n, offsets.data_ptr(),
+                                          C.byref(total), C.byref(bad), st),
+                   "rpt_text_rows_size")
+        if bad.value:
+            return None
+        out = torch.empty(int(total.value), dtype=torch.uint8, device=dev)
+        _abi.check(lib.rpt_text_rows_write(layout, x.data_ptr(), y.data_ptr(), z.data_ptr(),
+                                           tail.data_ptr(), n, offsets.data_ptr(),
+                                           out.data_ptr(), out.numel(), st),
+                   "rpt_text_rows_write")
+    return out
+
+
+def _tail_dtype(layout: int):
+    return (np.uint8, torch.uint8) if layout == _abi.TEXT_PLY else (np.int32, torch.int32)
+
+
+def _device_ok(layout: int, x, y, z, tail) -> bool:
+    """The arrays are what the kernel reads: float32 coordinates of one length and a uint8 [n][3]
+    / int32 [n] tail (numpy labels of another integer type qualify when they fit int32)."""
+    n = int(x.shape[0])
+    np_t, torch_t = _tail_dtype(layout)
+    for a in (x, y, z):
+        if a.ndim != 1 or int(a.shape[0]) != n:
+            return False
+        if a.dtype != (torch.float32 if is_torch(a) else np.float32):
+            return False
+    want = (n, 3) if layout == _abi.TEXT_PLY else (n,)
+    if tuple(tail.shape) != want:
+        return False
+    if is_torch(tail):
+        return tail.dtype == torch_t
+    if tail.dtype == np_t:
+        return True
+    if layout == _abi.TEXT_LABELS and tail.dtype.kind in "iu":
+        return n == 0 or (int(tail.min()) >= -2**31 and int(tail.max()) < 2**31)
+    return False
+
+
+def _to_dev(a, dtype, dev) -> torch.Tensor:
+    if not is_torch(a):
+        a = torch.from_numpy(np.ascontiguousarray(a))
+    return a.to(device=dev, dtype=dtype).contiguous()
+
+
+def _format(layout: int, x, y, z, tail, as_tensor: Optional[bool] = None):
+    host = format_ply_rows_host if layout == _abi.TEXT_PLY else format_label_rows_host
+    on_device = any(is_torch(a) and a.is_cuda for a in (x, y, z, tail))
+    want_torch = all(is_torch(a) for a in (x, y, z, tail)) if as_tensor is None else as_tensor
+    text = None
+    if (on_device or gpu_visible()) and _device_ok(layout, x, y, z, tail):
+        dev = next((a.device for a in (x, y, z, tail) if is_torch(a) and a.is_cuda),
+                   None) or torch.device("cuda", torch.cuda.current_device())
+        text = _device_rows(layout, _to_dev(x, torch.float32, dev),
+                            _to_dev(y, torch.float32, dev), _to_dev(z, torch.float32, dev),
+                            _to_dev(tail, _tail_dtype(layout)[1], dev))
+    if text is None:  # no GPU, other dtypes, or values outside the kernel's domain
+        raw = host(x, y, z, tail)
+        if not want_torch:
+            return raw
+        t = torch.frombuffer(bytearray(raw), dtype=torch.uint8) if raw else \
+            torch.empty(0, dtype=torch.uint8)
+        return t.to(x.device) if is_torch(x) else t
+    return text if want_torch else text.cpu().numpy().tobytes()
+
+
+def format_ply_rows(x, y, z, rgb, as_tensor: Optional[bool] = None):
+    """``"%.6f %.6f %.6f %d %d %d\\n"`` per point.  as_tensor: True keeps the text a tensor (on the
+    device when it was formed there) whatever the inputs are, False returns bytes."""
+    return _format(_abi.TEXT_PLY, x, y, z, rgb, as_tensor)
+
+
+def format_label_rows(x, y, z, labels, as_tensor: Optional[bool] = None):
+    """``"%.6f,%.6f,%.6f,%d\\n"`` per point; as_tensor as for format_ply_rows."""
+    return _format(_abi.TEXT_LABELS, x, y, z, labels, as_tensor)
+
+
+# ---- device text -> file ------------------------------------------------------------------------
+
+_pinned: list = []
+
+
+def _staging(nbytes: int, count: int):
+    size = min(max(nbytes, 1), _COPY_CHUNK)
+    while len(_pinned) < count:
+        _pinned.append(torch.empty(0, dtype=torch.uint8))
+    for k in range(count):
+        if _pinned[k].numel() < size:
+            _pinned[k] = torch.empty(size, dtype=torch.uint8, pin_memory=True)
+    return size, _pinned[:count]
+
+
+def write_text(fh, text) -> None:
+    """Append formatted rows to the binary file ``fh``: bytes as they are, a device tensor in
+    pieces through two pinned buffers (the copy of piece k+1 runs while piece k is written)."""
+    if not is_torch(text):
+        fh.write(text)
+        return
+    n = text.numel()
+    if n == 0:
+        return
+    if not text.is_cuda:
+        fh.write(text.numpy().tobytes())
+        return
+    pieces = -(-n // _COPY_CHUNK)
+    size, bufs = _staging(n, min(pieces, 2))
+    events = [torch.cuda.Event() for _ in bufs]
+    with torch.cuda.device(text.device):
+        def start(k):
+            lo = k * size
+            cnt = min(size, n - lo)
+            bufs[k % 2][:cnt].copy_(text[lo:lo + cnt], non_blocking=True)
+            events[k % 2].record()
+            return cnt
+
+        cnt = start(0)
+        for k in range(pieces):
+            nxt = start(k + 1) if k + 1 < pieces else 0
+            events[k % 2].synchronize()
+            fh.write(memoryview(bufs[k % 2].numpy())[:cnt])
+            cnt = nxt

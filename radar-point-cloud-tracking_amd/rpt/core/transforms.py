@@ -89,6 +89,58 @@ def sweep_to_point_cloud(sweep: RadarSweep, config: Optional[ProcessingConfig] =
     return PointCloud(x=x[:k].cpu().numpy(), y=y[:k].cpu().numpy(), z=z[:k].cpu().numpy())
 
 
+def simple_trig_tables(angles_rad) -> Tuple[np.ndarray, np.ndarray]:
+    """float32 cos/sin per row as sweep_to_points_simple evaluates them (transforms.py:117-118):
+    np.cos / np.sin over the 1-D array itself (numpy's contiguous float32 loop -- not the strided
+    column form of ``trig_tables``), then astype(float32).  Host values handed to the kernel."""
+    a = angles_rad.detach().cpu().numpy() if is_torch(angles_rad) else np.asarray(angles_rad)
+    return np.cos(a).astype(np.float32), np.sin(a).astype(np.float32)
+
+
+def sweep_to_points_simple(angles_rad, intensities, range_bin_width: float = 0.5,
+                           range_start: float = 0.0, min_intensity: float = 0.0,
+                           stride: int = 1):
+    """transforms.py:82-132: uniform range bins, x = range * cos, y = range * sin, z = intensity
+    for intensity > min_intensity (strict, compared in float32), every stride-th kept cell in
+    row-major order -- on the device (rpt_sweep_to_points).  numpy intensities give numpy
+    (x, y, z); a torch tensor gives tensors that stay on the device."""
+    want_torch = is_torch(intensities)
+    inten = intensities if want_torch else np.asarray(intensities)
+    if inten.dtype != (torch.float32 if want_torch else np.float32) or inten.ndim != 2:
+        raise NotImplementedError("rpt sweep_to_points_simple: a 2-D float32 sweep required")
+    rows, bins = (int(v) for v in inten.shape)
+    ranges = range_start + np.arange(bins, dtype=np.float32) * range_bin_width
+    if ranges.dtype != np.float32:
+        raise NotImplementedError("rpt sweep_to_points_simple: float32 range bins required")
+    c, s = simple_trig_tables(angles_rad)
+    if c.shape != (rows,):
+        raise ValueError(f"{c.shape[0] if c.ndim == 1 else c.shape} angles for {rows} sweep rows")
+    dev = require_gpu(inten.device if want_torch and inten.is_cuda else None)
+    stride = max(int(stride), 1)
+    cap = rows * bins // stride + 1
+    x = torch.empty(cap, dtype=torch.float32, device=dev)
+    y = torch.empty_like(x)
+    z = torch.empty_like(x)
+    k = 0
+    if rows and bins:
+        idev = to_device(inten, torch.float32, dev)
+        rdev = to_device(np.broadcast_to(ranges, (rows, bins)), torch.float32, dev)
+        cd = to_device(c, torch.float32, dev)
+        sd = to_device(s, torch.float32, dev)
+        nout = _abi.C.c_int64(0)
+        with torch.cuda.device(dev):
+            st = _abi.load().rpt_sweep_to_points(idev.data_ptr(), rdev.data_ptr(), cd.data_ptr(),
+                                                 sd.data_ptr(), rows, bins,
+                                                 float(np.float32(min_intensity)), stride,
+                                                 x.data_ptr(), y.data_ptr(), z.data_ptr(), cap,
+                                                 _abi.C.byref(nout), stream_handle(dev))
+        _abi.check(st, "rpt_sweep_to_points")
+        k = int(nout.value)
+    if want_torch:
+        return x[:k], y[:k], z[:k]
+    return x[:k].cpu().numpy(), y[:k].cpu().numpy(), z[:k].cpu().numpy()
+
+
 def subsample_cloud(cloud: PointCloud, max_points: int) -> Tuple[PointCloud, int]:
     """transforms.py:135-167 (host; unseeded random choice only above max_points)."""
     n = cloud.size
@@ -107,3 +159,24 @@ def apply_stride(cloud: PointCloud, stride: int) -> PointCloud:
     new_colors = cloud.colors[::stride] if cloud.colors is not None else None
     return PointCloud(x=cloud.x[::stride], y=cloud.y[::stride], z=cloud.z[::stride],
                       colors=new_colors)
+
+
+def apply_z_offset(cloud: PointCloud, offset: float) -> PointCloud:
+    """transforms.py:201-222: z + offset in the dtype of z (float32 + Python float = float32)."""
+    return PointCloud(x=cloud.x, y=cloud.y, z=cloud.z + offset, colors=cloud.colors)
+
+
+def intensity_to_colors(values: np.ndarray) -> np.ndarray:
+    """transforms.py:225-240: grey RGB from intensities clipped to 0..255 (host)."""
+    v = values.detach().cpu().numpy() if is_torch(values) else np.asarray(values)
+    clipped = np.clip(v, 0, 255).astype(np.uint8)
+    return np.stack([clipped, clipped, clipped], axis=1)
+
+
+def gain_to_colors(values, gain: int, gain_colors: dict):
+    """transforms.py:243-262: one constant RGB row per value, (180, 180, 180) for a gain without
+    a colour.  A torch ``values`` gives a uint8 tensor on its device."""
+    rgb = np.array(gain_colors.get(gain, (180, 180, 180)), dtype=np.uint8)
+    if is_torch(values):
+        return torch.from_numpy(rgb).to(values.device).repeat(values.numel(), 1)
+    return np.repeat(rgb[None, :], np.asarray(values).size, axis=0)

@@ -1,14 +1,60 @@
-"""Drop-in for ``radar_pipeline.core.writers.write_labels_csv`` (core/writers.py:65-81)."""
+"""Drop-in for ``radar_pipeline.core.writers.write_ply`` and ``write_labels_csv``
+(core/writers.py:13-46, :65-81).  The text rows of both are formed on the device when one is
+visible (rpt/core/text.py, csrc/text.hip) and by the reference's own expressions otherwise; the
+bytes written are the same either way."""
 from __future__ import annotations
 
 from pathlib import Path
 
 import numpy as np
 
+from .loaders import PointCloud
+
+
+def write_ply(path: Path, cloud: PointCloud) -> None:
+    """writers.py:13-46: ASCII PLY with uchar RGB, grey 180 without colours.  The members of
+    ``cloud`` may be numpy arrays or torch tensors (device tensors are formatted where they
+    are and reach the file through a pinned buffer)."""
+    from . import text
+
+    path = Path(path)
+    num_points = cloud.size
+    colors = cloud.colors
+    if colors is None:
+        colors = np.full((num_points, 3), 180, dtype=np.uint8)
+    header = ("ply\n"
+              "format ascii 1.0\n"
+              f"element vertex {num_points}\n"
+              "property float x\n"
+              "property float y\n"
+              "property float z\n"
+              "property uchar red\n"
+              "property uchar green\n"
+              "property uchar blue\n"
+              "end_header\n")
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with path.open("wb") as fh:
+        fh.write(header.encode("utf-8"))
+        text.write_text(fh, text.format_ply_rows(cloud.x, cloud.y, cloud.z, colors,
+                                                     as_tensor=True))
+
 
 def write_labels_csv(path: Path, coords: np.ndarray, labels: np.ndarray) -> None:
+    """writers.py:65-81.  (N, 3) float32 coordinates with int32-range integer labels go through
+    the device formatter when a GPU is visible; everything else is np.savetxt as before."""
+    from . import text
+
     path = Path(path)
     path.parent.mkdir(parents=True, exist_ok=True)
+    c = np.asarray(coords)
+    lab = np.asarray(labels)
+    if (text.gpu_visible() and c.ndim == 2 and c.shape[1] == 3 and c.dtype == np.float32
+            and lab.ndim == 1 and lab.dtype.kind in "iu" and len(lab) == len(c)):
+        rows = text.format_label_rows(c[:, 0], c[:, 1], c[:, 2], lab, as_tensor=True)
+        with path.open("wb") as fh:
+            fh.write(b"x,y,z,label\n")
+            text.write_text(fh, rows)
+        return
     arr = np.column_stack((coords, labels))
     np.savetxt(path, arr, fmt="%.6f,%.6f,%.6f,%d", header="x,y,z,label", comments="")
 

@@ -5,3 +5,9 @@ from .clustering import (  # noqa: F401
     process_ply_clustering,
     st_dbscan,
 )
+from .point_cloud import (  # noqa: F401
+    build_stacked_clouds,
+    combine_clouds,
+    find_gain_sweeps,
+    load_points_from_csv,
+)
