@@ -27,7 +27,9 @@
  *   rpt_fuse_gains_max               fuse_gains_max PointCloudWork/5_gain_fusion_ply_builder.py:222-273
  *   rpt_csv_*                        pd.read_csv + fillna/to_numpy of load_radar_csv :189-211
  *   rpt_text_rows_size /             the per-point f-string of write_ply radar_pipeline/core/writers.py:45-46
- *   rpt_text_rows_write              and np.savetxt(fmt="%.6f,%.6f,%.6f,%d") of write_labels_csv :79-81
+ *   rpt_text_rows_write              and np.savetxt(fmt="%.6f,%.6f,%.6f,%d") of write_labels_csv :79-81;
+ *                                    the float32 to_csv rows of convert_single_csv processors/cartesian.py:46-53
+ *   rpt_float32_repr                 np.float32(v).astype(str) (host; the code of that layout)
  *   rpt_synth_echo                   (bench/test input generator; no reference counterpart)
  */
 #ifndef RPT_H
@@ -253,14 +255,29 @@ int32_t rpt_fuse_gains_max(const float* x, const float* y, const float* intensit
  * rpt_text_rows_write: the rows at out + row_offsets[i] (out dev u8 [out_bytes], out_bytes >=
  * the total).  The inputs must be those given to rpt_text_rows_size; a row whose length does not
  * match its offsets, and a block of rows whose range does not lie inside [0, out_bytes), are
- * skipped -- nothing is written outside out whatever the inputs hold.  No sync. */
-enum { RPT_TEXT_PLY = 0, RPT_TEXT_LABELS = 1 };
+ * skipped -- nothing is written outside out whatever the inputs hold.  No sync.
+ *
+ *   RPT_TEXT_XYZ_REPR  "repr(x),repr(y),repr(z)\n"  x, y, z f32 [n], tail unused (may be NULL)
+ * the rows DataFrame({"x", "y", "z"}).to_csv(index=False) writes for float32 columns
+ * (radar_pipeline/processors/cartesian.py:46-53): repr(v) is np.float32(v).astype(str), the
+ * shortest decimal that reads back as v (end points of the rounding interval included for an even
+ * mantissa, the candidate nearest v among those of equal length), positional with ".0" / "0."
+ * for 1e-4 <= |v| < 1e16 and zero, d[.ddd]e+XX otherwise; csrc/repr32.h has the rules.  At most
+ * 19 bytes a value, 60 a row.  Domain: every finite value; a row holding NaN or inf is counted
+ * in *n_unsupported_host (pandas writes an empty field / "inf": the host formatter's business). */
+enum { RPT_TEXT_PLY = 0, RPT_TEXT_LABELS = 1, RPT_TEXT_XYZ_REPR = 2 };
 int32_t rpt_text_rows_size(int32_t layout, const float* x, const float* y, const float* z,
                            const void* tail, int64_t n, int64_t* row_offsets /*dev [n+1]*/,
                            int64_t* total_host, int64_t* n_unsupported_host, void* stream);
 int32_t rpt_text_rows_write(int32_t layout, const float* x, const float* y, const float* z,
                             const void* tail, int64_t n, const int64_t* row_offsets /*dev*/,
                             uint8_t* out /*dev [out_bytes]*/, int64_t out_bytes, void* stream);
+
+/* Host only (no GPU): the text of RPT_TEXT_XYZ_REPR per value, by the code the kernels run.
+ * out + RPT_FLOAT32_REPR_SLOT * i holds repr(v[i]) padded with NULs, len[i] its length (<= 19);
+ * NaN and inf give len 0 and an all-NUL slot. */
+#define RPT_FLOAT32_REPR_SLOT 20
+int32_t rpt_float32_repr(const float* v, int64_t n, char* out /*[n][20]*/, int32_t* len /*[n]*/);
 
 /* ---- K9: per-(frame, label) cluster summaries ---------------------------------------
  * point_frame[n] (dev, i32, non-decreasing frame slot per point), labels[n] from

@@ -329,12 +329,16 @@ int32_t rpt_infer_time_from_colors(const uint8_t* colors, int64_t n, const float
                                      rpt::as_stream(stream));
 }
 
+static bool text_layout_ok(int32_t layout) {
+  return layout == RPT_TEXT_PLY || layout == RPT_TEXT_LABELS || layout == RPT_TEXT_XYZ_REPR;
+}
+
 int32_t rpt_text_rows_size(int32_t layout, const float* x, const float* y, const float* z,
                            const void* tail, int64_t n, int64_t* row_offsets,
                            int64_t* total_host, int64_t* n_unsupported_host, void* stream) {
   rpt::clear_error();
-  if ((layout != RPT_TEXT_PLY && layout != RPT_TEXT_LABELS) || n < 0 || !row_offsets ||
-      !total_host || !n_unsupported_host || (n > 0 && (!x || !y || !z || !tail))) {
+  if (!text_layout_ok(layout) || n < 0 || !row_offsets || !total_host || !n_unsupported_host ||
+      (n > 0 && (!x || !y || !z || (!tail && layout != RPT_TEXT_XYZ_REPR)))) {
     rpt::set_error("rpt_text_rows_size: bad arguments");
     return RPT_EINVAL;
   }
@@ -350,8 +354,9 @@ int32_t rpt_text_rows_write(int32_t layout, const float* x, const float* y, cons
                             const void* tail, int64_t n, const int64_t* row_offsets,
                             uint8_t* out, int64_t out_bytes, void* stream) {
   rpt::clear_error();
-  if ((layout != RPT_TEXT_PLY && layout != RPT_TEXT_LABELS) || n < 0 || out_bytes < 0 ||
-      (n > 0 && (!x || !y || !z || !tail || !row_offsets || (out_bytes > 0 && !out)))) {
+  if (!text_layout_ok(layout) || n < 0 || out_bytes < 0 ||
+      (n > 0 && (!x || !y || !z || (!tail && layout != RPT_TEXT_XYZ_REPR) || !row_offsets ||
+                 (out_bytes > 0 && !out)))) {
     rpt::set_error("rpt_text_rows_write: bad arguments");
     return RPT_EINVAL;
   }

@@ -16,7 +16,13 @@
 // block's rows are contiguous in the output, so they are staged in LDS (at most 256 * 81 bytes)
 // at the same 16-byte phase as their place in out and then copied by the whole block: 16-byte
 // vector stores for the aligned interior, byte stores for the ragged head and tail.
+//
+// A third layout, RPT_TEXT_XYZ_REPR, goes through the same two kernels with another row type: the
+// "repr(x),repr(y),repr(z)\n" rows pandas' to_csv writes for float32 columns
+// (processors/cartesian.py:46-53), each value the shortest round-trip decimal of repr32.h (at most
+// 19 bytes, 60 a row).  Its domain is every finite value.
 #include "common.h"
+#include "repr32.h"
 
 namespace rpt {
 namespace {
@@ -121,6 +127,43 @@ struct Row {
   int len;
 };
 
+struct ReprRow {
+  repr32::Dec c[3];
+  int len;
+};
+
+template <int LAYOUT>
+struct RowOf {
+  typedef Row type;
+};
+template <>
+struct RowOf<RPT_TEXT_XYZ_REPR> {
+  typedef ReprRow type;
+};
+
+template <int LAYOUT>
+__device__ __forceinline__ void load_row(const float* __restrict__ x, const float* __restrict__ y,
+                                         const float* __restrict__ z, const void* __restrict__,
+                                         int64_t i, ReprRow* r) {
+  const bool okx = repr32::decimal(__float_as_uint(x[i]), &r->c[0]);
+  const bool oky = repr32::decimal(__float_as_uint(y[i]), &r->c[1]);
+  const bool okz = repr32::decimal(__float_as_uint(z[i]), &r->c[2]);
+  // 2 commas + newline
+  r->len = okx && oky && okz
+               ? 3 + repr32::length(r->c[0]) + repr32::length(r->c[1]) + repr32::length(r->c[2])
+               : -1;
+}
+
+template <int LAYOUT>
+__device__ __forceinline__ void put_row(uint8_t* p, const ReprRow& r) {
+  p = repr32::put(p, r.c[0]);
+  *p++ = ',';
+  p = repr32::put(p, r.c[1]);
+  *p++ = ',';
+  p = repr32::put(p, r.c[2]);
+  *p = '\n';
+}
+
 template <int LAYOUT>
 __device__ __forceinline__ void load_row(const float* __restrict__ x, const float* __restrict__ y,
                                          const float* __restrict__ z,
@@ -147,6 +190,28 @@ __device__ __forceinline__ void load_row(const float* __restrict__ x, const floa
 }
 
 template <int LAYOUT>
+__device__ __forceinline__ void put_row(uint8_t* p, const Row& r) {
+  constexpr uint8_t sep = LAYOUT == RPT_TEXT_PLY ? ' ' : ',';
+  p = put_float(p, r.c[0]);
+  *p++ = sep;
+  p = put_float(p, r.c[1]);
+  *p++ = sep;
+  p = put_float(p, r.c[2]);
+  *p++ = sep;
+  if (LAYOUT == RPT_TEXT_PLY) {
+    p = put_u32(p, r.t[0]);
+    *p++ = ' ';
+    p = put_u32(p, r.t[1]);
+    *p++ = ' ';
+    p = put_u32(p, r.t[2]);
+  } else {
+    if (r.t[1]) *p++ = '-';
+    p = put_u32(p, r.t[0]);
+  }
+  *p = '\n';
+}
+
+template <int LAYOUT>
 __global__ void __launch_bounds__(kBlock)
 k_text_len(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
            const void* __restrict__ tail, int64_t n, int32_t* __restrict__ lens,
@@ -154,7 +219,7 @@ k_text_len(const float* __restrict__ x, const float* __restrict__ y, const float
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   bool bad = false;
   if (i < n) {
-    Row r;
+    typename RowOf<LAYOUT>::type r;
     load_row<LAYOUT>(x, y, z, tail, i, &r);
     bad = r.len < 0;
     lens[i] = bad ? 0 : r.len;
@@ -179,30 +244,12 @@ k_text_write(const float* __restrict__ x, const float* __restrict__ y,
   const int hi = lo + (int)(b1 - b0);
   const int64_t i = first + threadIdx.x;
   if (i < last) {
-    Row r;
+    typename RowOf<LAYOUT>::type r;
     load_row<LAYOUT>(x, y, z, tail, i, &r);
     const int64_t o = off[i], o1 = off[i + 1];
     // a row is staged only where its own length says it ends, inside the block's range
     if (r.len > 0 && o >= b0 && o1 - o == r.len && o1 <= b1) {
-      uint8_t* p = stage + lo + (int)(o - b0);
-      constexpr uint8_t sep = LAYOUT == RPT_TEXT_PLY ? ' ' : ',';
-      p = put_float(p, r.c[0]);
-      *p++ = sep;
-      p = put_float(p, r.c[1]);
-      *p++ = sep;
-      p = put_float(p, r.c[2]);
-      *p++ = sep;
-      if (LAYOUT == RPT_TEXT_PLY) {
-        p = put_u32(p, r.t[0]);
-        *p++ = ' ';
-        p = put_u32(p, r.t[1]);
-        *p++ = ' ';
-        p = put_u32(p, r.t[2]);
-      } else {
-        if (r.t[1]) *p++ = '-';
-        p = put_u32(p, r.t[0]);
-      }
-      *p = '\n';
+      put_row<LAYOUT>(stage + lo + (int)(o - b0), r);
     } else if (o >= b0 && o1 >= o && o1 <= b1) {
       // skipped row with a consistent slot: defined bytes instead of stale LDS
       for (int64_t k = o; k < o1; ++k) stage[lo + (int)(k - b0)] = ' ';
@@ -239,9 +286,12 @@ int32_t text_rows_size(int32_t layout, const float* x, const float* y, const flo
   if (layout == RPT_TEXT_PLY)
     hipLaunchKernelGGL(k_text_len<RPT_TEXT_PLY>, grid, dim3(kBlock), 0, st, x, y, z, tail, n,
                        lens, n_bad);
-  else
+  else if (layout == RPT_TEXT_LABELS)
     hipLaunchKernelGGL(k_text_len<RPT_TEXT_LABELS>, grid, dim3(kBlock), 0, st, x, y, z, tail, n,
                        lens, n_bad);
+  else
+    hipLaunchKernelGGL(k_text_len<RPT_TEXT_XYZ_REPR>, grid, dim3(kBlock), 0, st, x, y, z, tail,
+                       n, lens, n_bad);
   RPT_CHECK_LAUNCH();
   RPT_TRY(exclusive_scan_total_i32_to_i64(lens, row_offsets, n, st));
   int64_t tot = 0;
@@ -262,8 +312,11 @@ int32_t text_rows_write(int32_t layout, const float* x, const float* y, const fl
   if (layout == RPT_TEXT_PLY)
     hipLaunchKernelGGL(k_text_write<RPT_TEXT_PLY>, grid, dim3(kBlock), 0, st, x, y, z, tail, n,
                        row_offsets, out, out_bytes);
-  else
+  else if (layout == RPT_TEXT_LABELS)
     hipLaunchKernelGGL(k_text_write<RPT_TEXT_LABELS>, grid, dim3(kBlock), 0, st, x, y, z, tail,
+                       n, row_offsets, out, out_bytes);
+  else
+    hipLaunchKernelGGL(k_text_write<RPT_TEXT_XYZ_REPR>, grid, dim3(kBlock), 0, st, x, y, z, tail,
                        n, row_offsets, out, out_bytes);
   RPT_CHECK_LAUNCH();
   return RPT_OK;

@@ -24,6 +24,8 @@ ECHO_U8 = 1
 
 TEXT_PLY = 0
 TEXT_LABELS = 1
+TEXT_XYZ_REPR = 2
+FLOAT32_REPR_SLOT = 20
 
 c_f32p = C.POINTER(C.c_float)
 c_f64p = C.POINTER(C.c_double)
@@ -254,6 +256,7 @@ _SIGS = [
      [C.c_int32, vp, vp, vp, vp, C.c_int64, vp, c_i64p, c_i64p, vp]),
     ("rpt_text_rows_write", C.c_int32,
      [C.c_int32, vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int64, vp]),
+    ("rpt_float32_repr", C.c_int32, [vp, C.c_int64, vp, vp]),
     ("rpt_csv_count_rows", C.c_int32, [C.POINTER(C.c_char_p), C.c_int32, c_i64p, C.c_int32]),
     ("rpt_csv_parse_sweeps", C.c_int32,
      [C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, c_f32p, c_f32p,

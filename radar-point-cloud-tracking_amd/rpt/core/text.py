@@ -7,6 +7,11 @@ integers for finite ``|v| < 2**40``.  Inputs outside that domain (NaN, inf, larg
 inputs of other dtypes and hosts without a GPU take the host formatter below, which evaluates the
 reference expression itself -- same bytes, at CPython's speed.
 
+A third layout are the ``x,y,z`` rows ``DataFrame.to_csv`` writes for float32 columns
+(radar_pipeline/processors/cartesian.py:46-53): every value as ``np.float32(v).astype(str)``, the
+shortest decimal that reads back as the value (csrc/repr32.h).  The kernel covers every finite
+value; NaN (an empty field) and inf go to the host formatter, which is the pandas expression.
+
 Torch device tensors in -> a device ``uint8`` tensor out; numpy in -> ``bytes`` out.
 """
 from __future__ import annotations
@@ -66,28 +71,39 @@ def format_label_rows_host(x, y, z, labels) -> bytes:
     return "".join(parts).encode()
 
 
+def format_xyz_rows_host(x, y, z) -> bytes:
+    """The body of ``pd.DataFrame({"x": x, "y": y, "z": z}).to_csv(index=False)``
+    (cartesian.py:46-53): the text without its ``x,y,z`` header line."""
+    import pandas as pd
+
+    csv = pd.DataFrame({"x": _np(x), "y": _np(y), "z": _np(z)}).to_csv(index=False)
+    return csv[csv.index("\n") + 1:].encode()
+
+
 # ---- device formatter -------------------------------------------------------------------------
 
 def _device_rows(layout: int, x, y, z, tail) -> Optional[torch.Tensor]:
-    """Rows of contiguous device tensors (x, y, z float32 [n]; tail uint8 [n][3] or int32 [n]) as
-    a device uint8 tensor, or None when a row is outside the kernel's domain."""
+    """Rows of contiguous device tensors (x, y, z float32 [n]; tail uint8 [n][3], int32 [n] or
+    None for the layout without one) as a device uint8 tensor, or None when a row is outside the
+    kernel's domain."""
     dev = x.device
     n = x.numel()
     lib = _abi.load()
+    tail_ptr = tail.data_ptr() if tail is not None else None
     offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
     total = C.c_int64(0)
     bad = C.c_int64(0)
     with torch.cuda.device(dev):
         st = stream_handle(dev)
         _abi.check(lib.rpt_text_rows_size(layout, x.data_ptr(), y.data_ptr(), z.data_ptr(),
-                                          tail.data_ptr(), n, offsets.data_ptr(),
+                                          tail_ptr, n, offsets.data_ptr(),
                                           C.byref(total), C.byref(bad), st),
                    "rpt_text_rows_size")
         if bad.value:
             return None
         out = torch.empty(int(total.value), dtype=torch.uint8, device=dev)
         _abi.check(lib.rpt_text_rows_write(layout, x.data_ptr(), y.data_ptr(), z.data_ptr(),
-                                           tail.data_ptr(), n, offsets.data_ptr(),
+                                           tail_ptr, n, offsets.data_ptr(),
                                            out.data_ptr(), out.numel(), st),
                    "rpt_text_rows_write")
     return out
@@ -100,13 +116,17 @@ def _tail_dtype(layout: int):
 def _device_ok(layout: int, x, y, z, tail) -> bool:
     """The arrays are what the kernel reads: float32 coordinates of one length and a uint8 [n][3]
     / int32 [n] tail (numpy labels of another integer type qualify when they fit int32)."""
+    if x.ndim != 1:
+        return False
     n = int(x.shape[0])
-    np_t, torch_t = _tail_dtype(layout)
     for a in (x, y, z):
         if a.ndim != 1 or int(a.shape[0]) != n:
             return False
         if a.dtype != (torch.float32 if is_torch(a) else np.float32):
             return False
+    if layout == _abi.TEXT_XYZ_REPR:
+        return True
+    np_t, torch_t = _tail_dtype(layout)
     want = (n, 3) if layout == _abi.TEXT_PLY else (n,)
     if tuple(tail.shape) != want:
         return False
@@ -126,18 +146,19 @@ def _to_dev(a, dtype, dev) -> torch.Tensor:
 
 
 def _format(layout: int, x, y, z, tail, as_tensor: Optional[bool] = None):
-    host = format_ply_rows_host if layout == _abi.TEXT_PLY else format_label_rows_host
-    on_device = any(is_torch(a) and a.is_cuda for a in (x, y, z, tail))
-    want_torch = all(is_torch(a) for a in (x, y, z, tail)) if as_tensor is None else as_tensor
+    arrays = (x, y, z) if layout == _abi.TEXT_XYZ_REPR else (x, y, z, tail)
+    on_device = any(is_torch(a) and a.is_cuda for a in arrays)
+    want_torch = all(is_torch(a) for a in arrays) if as_tensor is None else as_tensor
     text = None
     if (on_device or gpu_visible()) and _device_ok(layout, x, y, z, tail):
-        dev = next((a.device for a in (x, y, z, tail) if is_torch(a) and a.is_cuda),
+        dev = next((a.device for a in arrays if is_torch(a) and a.is_cuda),
                    None) or torch.device("cuda", torch.cuda.current_device())
         text = _device_rows(layout, _to_dev(x, torch.float32, dev),
                             _to_dev(y, torch.float32, dev), _to_dev(z, torch.float32, dev),
+                            None if layout == _abi.TEXT_XYZ_REPR else
                             _to_dev(tail, _tail_dtype(layout)[1], dev))
     if text is None:  # no GPU, other dtypes, or values outside the kernel's domain
-        raw = host(x, y, z, tail)
+        raw = _HOST[layout](*arrays)
         if not want_torch:
             return raw
         t = torch.frombuffer(bytearray(raw), dtype=torch.uint8) if raw else \
@@ -155,6 +176,16 @@ def format_ply_rows(x, y, z, rgb, as_tensor: Optional[bool] = None):
 def format_label_rows(x, y, z, labels, as_tensor: Optional[bool] = None):
     """``"%.6f,%.6f,%.6f,%d\\n"`` per point; as_tensor as for format_ply_rows."""
     return _format(_abi.TEXT_LABELS, x, y, z, labels, as_tensor)
+
+
+def format_xyz_rows(x, y, z, as_tensor: Optional[bool] = None):
+    """``"repr(x),repr(y),repr(z)\\n"`` per point, the float32 rows of ``to_csv``; as_tensor as for
+    format_ply_rows."""
+    return _format(_abi.TEXT_XYZ_REPR, x, y, z, None, as_tensor)
+
+
+_HOST = {_abi.TEXT_PLY: format_ply_rows_host, _abi.TEXT_LABELS: format_label_rows_host,
+         _abi.TEXT_XYZ_REPR: format_xyz_rows_host}
 
 
 # ---- device text -> file ------------------------------------------------------------------------

@@ -53,13 +53,10 @@ def polar_to_cartesian(angles_rad, ranges):
     return x.cpu().numpy(), y.cpu().numpy()
 
 
-def sweep_to_point_cloud(sweep: RadarSweep, config: Optional[ProcessingConfig] = None,
-                         radar_config: Optional[RadarConfig] = None) -> PointCloud:
-    """transforms.py:37-79: threshold (strict >) + row-major flatten + stride, on the device."""
-    if config is None:
-        config = ProcessingConfig()
-    if radar_config is None:
-        radar_config = RadarConfig()
+def sweep_points_device(sweep: RadarSweep, threshold: float, stride: int = 1):
+    """The thresholded points of a loaded sweep as device tensors (x, y, z): strict ``>`` against
+    the threshold cast to float32, row-major order, every stride-th kept cell
+    (rpt_sweep_to_points)."""
     a = np.asarray(sweep.angles_rad)
     c = np.cos(a[:, None])[:, 0]
     s = np.sin(a[:, None])[:, 0]
@@ -73,20 +70,32 @@ def sweep_to_point_cloud(sweep: RadarSweep, config: Optional[ProcessingConfig] =
     rdev = to_device(np.broadcast_to(ranges, inten.shape), torch.float32, dev)
     cd = to_device(c.astype(np.float32), torch.float32, dev)
     sd = to_device(s.astype(np.float32), torch.float32, dev)
-    stride = max(int(config.point_stride), 1)
+    stride = max(int(stride), 1)
     cap = rows * bins // stride + 1
     x = torch.empty(cap, dtype=torch.float32, device=dev)
     y = torch.empty_like(x)
     z = torch.empty_like(x)
     nout = _abi.C.c_int64(0)
-    st = _abi.load().rpt_sweep_to_points(idev.data_ptr(), rdev.data_ptr(), cd.data_ptr(),
-                                         sd.data_ptr(), rows, bins,
-                                         float(np.float32(config.intensity_threshold)), stride,
-                                         x.data_ptr(), y.data_ptr(), z.data_ptr(), cap,
-                                         _abi.C.byref(nout), stream_handle(dev))
+    with torch.cuda.device(dev):
+        st = _abi.load().rpt_sweep_to_points(idev.data_ptr(), rdev.data_ptr(), cd.data_ptr(),
+                                             sd.data_ptr(), rows, bins,
+                                             float(np.float32(threshold)), stride,
+                                             x.data_ptr(), y.data_ptr(), z.data_ptr(), cap,
+                                             _abi.C.byref(nout), stream_handle(dev))
     _abi.check(st, "rpt_sweep_to_points")
     k = int(nout.value)
-    return PointCloud(x=x[:k].cpu().numpy(), y=y[:k].cpu().numpy(), z=z[:k].cpu().numpy())
+    return x[:k], y[:k], z[:k]
+
+
+def sweep_to_point_cloud(sweep: RadarSweep, config: Optional[ProcessingConfig] = None,
+                         radar_config: Optional[RadarConfig] = None) -> PointCloud:
+    """transforms.py:37-79: threshold (strict >) + row-major flatten + stride, on the device."""
+    if config is None:
+        config = ProcessingConfig()
+    if radar_config is None:
+        radar_config = RadarConfig()
+    x, y, z = sweep_points_device(sweep, config.intensity_threshold, config.point_stride)
+    return PointCloud(x=x.cpu().numpy(), y=y.cpu().numpy(), z=z.cpu().numpy())
 
 
 def simple_trig_tables(angles_rad) -> Tuple[np.ndarray, np.ndarray]:

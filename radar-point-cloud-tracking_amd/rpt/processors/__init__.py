@@ -1,4 +1,9 @@
 """Drop-in for ``radar_pipeline.processors`` (hot-path members only)."""
+from .cartesian import (  # noqa: F401
+    aligned_inputs,
+    convert_batch_aligned,
+    convert_single_csv,
+)
 from .clustering import (  # noqa: F401
     cluster_point_cloud,
     infer_time_from_colors,

@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
 """Text-row formatter benchmark: device tensors -> file on disk, per layout.
 
-    python tools/text_bench.py [--rows 2000000] [--runs 3] [--out result.json]
+    python tools/text_bench.py [--rows 2000000] [--runs 3] [--legs labels,ply,xyz]
+                               [--out result.json]
 
-For each layout (labels CSV, PLY vertex lines) the same seeded rows are written
+For each layout (labels CSV, PLY vertex lines, the x,y,z CSV of convert) the same seeded rows are
+written
   device: rpt_text_rows_size + rpt_text_rows_write on the GPU, the text copied through pinned
           buffers into the file (what write_labels_csv / write_ply do when a GPU is visible);
   host:   labels: np.savetxt(fmt="%.6f,%.6f,%.6f,%d") on the host arrays -- write_labels_csv as it
           was before the formatter; PLY: the host formatter of rpt.core.text (the reference's
-          expression), which write_ply uses without a GPU.
+          expression), which write_ply uses without a GPU; xyz: the pandas expression of
+          convert_single_csv, DataFrame({"x", "y", "z"}).to_csv(path, index=False).
 The two are run alternately, `--runs` times each after one warm-up of the device path; medians and
 every single time are reported, the files are compared byte for byte, and the two kernels are
 timed alone with device events.  Needs a GPU: there is nothing to measure without one.
@@ -33,6 +36,7 @@ def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--rows", type=int, default=2_000_000)
     ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--legs", default="labels,ply,xyz", help="comma-separated subset of the legs")
     ap.add_argument("--dir", type=Path, default=None, help="where the files are written")
     ap.add_argument("--out", type=Path, default=None, help="also write the JSON result here")
     args = ap.parse_args()
@@ -78,6 +82,16 @@ def main() -> int:
                 s = slice(lo, lo + (1 << 18))
                 fh.write(text.format_ply_rows_host(xyz[0][s], xyz[1][s], xyz[2][s], rgb[s]))
 
+    def device_xyz(path):
+        with open(path, "wb") as fh:
+            fh.write(b"x,y,z\n")
+            text.write_text(fh, text.format_xyz_rows(*d_xyz))
+
+    def host_xyz(path):
+        import pandas as pd
+
+        pd.DataFrame({"x": xyz[0], "y": xyz[1], "z": xyz[2]}).to_csv(path, index=False)
+
     def timed(fn, path):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -92,7 +106,7 @@ def main() -> int:
         off = torch.empty(n + 1, dtype=torch.int64, device=dev)
         total, bad = C.c_int64(0), C.c_int64(0)
         st = torch.cuda.current_stream(dev).cuda_stream
-        ptrs = [a.data_ptr() for a in d_xyz] + [tail.data_ptr()]
+        ptrs = [a.data_ptr() for a in d_xyz] + [tail.data_ptr() if tail is not None else None]
         size_ms, write_ms = [], []
         out = None
         for _ in range(args.runs + 1):
@@ -113,9 +127,13 @@ def main() -> int:
                 "write_ms": statistics.median(write_ms[1:])}
 
     result = {"rows": n, "runs": args.runs, "device": torch.cuda.get_device_name(0)}
+    legs = [k for k in args.legs.split(",") if k]
     for name, dfn, hfn, layout, tail in (
             ("labels", device_labels, host_labels, _abi.TEXT_LABELS, d_labels),
-            ("ply", device_ply, host_ply, _abi.TEXT_PLY, d_rgb)):
+            ("ply", device_ply, host_ply, _abi.TEXT_PLY, d_rgb),
+            ("xyz", device_xyz, host_xyz, _abi.TEXT_XYZ_REPR, None)):
+        if name not in legs:
+            continue
         dp, hp = out_dir / f"{name}_device.txt", out_dir / f"{name}_host.txt"
         timed(dfn, dp)  # warm-up: code objects, pinned buffers
         dt, ht = [], []
@@ -136,7 +154,7 @@ def main() -> int:
         args.out.write_text(line + "\n")
     if tmp:
         tmp.cleanup()
-    ok = all(result[k]["files_identical"] for k in ("labels", "ply"))
+    ok = all(result[k]["files_identical"] for k in legs if k in result)
     return 0 if ok else 1
 
 
