@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "ab_switches.h"  // ab(): the A/B build's switches, constants in the shipped build
 #include "host_common.h"
 
 namespace rpt {
@@ -25,18 +26,6 @@ namespace rpt {
 #define RPT_CHECK_LAUNCH() RPT_HIP(hipGetLastError())
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
-// A/B switches (RPT_* environment variables selecting a replaced kernel form for same-box
-// measurements) exist only in the A/B build (-DRPT_AB, tools/ab_*.sh): the shipped librpt.so
-// ignores the environment and always runs the default forms the parity suite covers.
-inline const char* ab_env(const char* name) {
-#ifdef RPT_AB
-  return std::getenv(name);
-#else
-  (void)name;
-  return nullptr;
-#endif
-}
 
 // Waits for the work queued on st so far by polling an event (readback latency; prims.hip).
 int32_t wait_stream(hipStream_t st);  // also reports device faults (check_device_faults)

@@ -663,15 +663,6 @@ int32_t bounds_xy(const float* x, const float* y, int64_t n, float* out4, hipStr
   return RPT_OK;
 }
 
-// RPT_LAND_U8=0: the int32 + float64 atomics kernel also for u8 points (A/B)
-static bool land_u8_enabled() {
-  static const bool on = [] {
-    const char* e = ab_env("RPT_LAND_U8");
-    return !(e && std::atoi(e) == 0);
-  }();
-  return on;
-}
-
 // the grid's counts and sums (and a caller's 64-bit counter) zeroed in ONE launch: two fills
 // and a third for the counter each cost a launch right after the host-synchronous bounds
 // readback, when the GPU idles on the host issuing them
@@ -710,7 +701,7 @@ int32_t land_grid_cells(const float* x, const float* y, const float* val, int64_
   RPT_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
   const int gb = grid_for(n, kGridBlock, std::max(n_cu, 1));
   if (u8_vals && lds_u8 <= 150 * 1024 && (n + gb - 1) / gb < (int64_t(1) << 24) &&
-      land_u8_enabled()) {
+      ab().land_u8) {
     RPT_HIP(hipFuncSetAttribute((const void*)k_land_grid_lds_u8,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_u8));
     hipLaunchKernelGGL(k_land_grid_lds_u8, dim3(gb), dim3(kGridBlock), lds_u8, st, x, y, val, n,

@@ -949,16 +949,9 @@ inline uint32_t u8_k(int T) {
 }
 
 // k_expand_write: a persistent grid (8 blocks per CU of the 256; each walks a contiguous tile
-// range).  RPT_K1_EXPAND=0 keeps the wave-per-group write for A/B runs.
+// range).  ab().k1_expand off keeps the wave-per-group write for A/B runs.
 constexpr int kExpandBlocks = 2048;
 constexpr int kListBlocks = 2048;  // blocks of the unstaged groups' write (at most)
-inline bool expand_write_enabled() {
-  static const bool on = [] {
-    const char* e = ab_env("RPT_K1_EXPAND");
-    return !(e && std::atoi(e) == 0);
-  }();
-  return on;
-}
 
 template <class T>
 int32_t count_impl(const T* echo, int64_t n_files, int rows, int bins, float thr, int stride,
@@ -1046,7 +1039,7 @@ int32_t write_impl(const T* echo, int64_t n_files, int rows, int bins, float thr
     const int grid = grid_for(n_groups, kWavesPerBlock, 16384);
     const int T8 = u8_threshold(thr);
     const auto* e8 = reinterpret_cast<const uint8_t*>(echo);
-    if (entries && expand_write_enabled() && stride < (1 << 23) &&
+    if (entries && ab().k1_expand && stride < (1 << 23) &&
         n_files * (int64_t)rows * 1024 < (int64_t(1) << kGsBits)) {
       // staged entries: outputs to threads (k_expand_write); the few unstaged groups listed by
       // k_group_starts are written by the wave-per-group kernel

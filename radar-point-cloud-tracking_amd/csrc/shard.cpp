@@ -825,12 +825,8 @@ int32_t rpt_shard_polar(rpt_shard* h, const rpt_stack_params* p, const void* ech
   RPT_TRY(S.down.ensure(down_bytes, st));
   const bool grouped = p->echo_dtype == RPT_ECHO_U8 && p->bins == 1024 &&
                        (uintptr_t)echo % 16 == 0;
-  if (S.k1_staged < 0) {
-    const char* e = ab_env("RPT_K1_STAGE");
-    S.k1_staged = (e && std::atoi(e) == 0) ? 0 : 1;
-  }
   uint32_t* mk = nullptr;  // staged kept samples, as in rpt_stack_run
-  if (grouped && S.k1_staged) {
+  if (grouped && ab().k1_stage) {
     RPT_TRY(S.k1_stage.ensure((size_t)polar_stage_words(n_files, p->rows), st));
     mk = S.k1_stage.p;
   }

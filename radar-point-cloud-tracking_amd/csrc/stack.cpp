@@ -136,15 +136,11 @@ int32_t rpt_stack::run(const rpt_stack_params& p, const void* echo, const float*
   RPT_TRY(row_prefix.ensure((size_t)n_files * p.rows + 1, st));
   // u8 sweeps of 1024 bins: the count pass stages the kept samples of every group that keeps at
   // most 128 of them (the sparse radar case) and the write pass reads those instead of the echo,
-  // so K1 reads the echo once (RPT_K1_STAGE=0: two full reads)
+  // so K1 reads the echo once (ab().k1_stage off: two full reads)
   const bool grouped = p.echo_dtype == RPT_ECHO_U8 && p.bins == 1024 &&
                        (uintptr_t)echo % 16 == 0;
-  if (k1_staged < 0) {
-    const char* e = ab_env("RPT_K1_STAGE");
-    k1_staged = (e && std::atoi(e) == 0) ? 0 : 1;
-  }
   uint32_t* mk = nullptr;
-  if (grouped && k1_staged) {
+  if (grouped && ab().k1_stage) {
     RPT_TRY(k1_stage.ensure((size_t)polar_stage_words(n_files, p.rows), st));
     mk = k1_stage.p;
   }

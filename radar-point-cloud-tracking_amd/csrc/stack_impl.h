@@ -206,7 +206,6 @@ struct rpt_stack {
   DevBuf<uint8_t> land_mask;
   DevBuf<uint32_t> k1_stage;           // K1 staged kept samples (count pass -> write pass)
   DevBuf<uint32_t> k1_bnd;             // K1 write's xy bounds + block partials
-  int k1_staged = -1;                  // RPT_K1_STAGE (default on), read once
   DevBuf<uint8_t> bnd;                 // ST-DBSCAN bounds (+ partials) of the kept points
   std::vector<char> dbscan_bounds;     // their host copy, from the land readback
   PinnedBuf up, down;  // host staging: uploads (edges, offsets), readbacks

@@ -486,58 +486,6 @@ constexpr int kBucketBlock = 1024;
 constexpr int kBucketCells = 16384;  // max per-slab cells for the LDS histogram (<= 64 KiB)
 constexpr int kBucketU = 4;          // points per thread per round (loads in flight together)
 constexpr int64_t kChunkPts = 16384;  // points per slab-bucket block when a slab is split
-// RPT_SLAB_CHUNKS=k: k blocks per slab (1 = the single-block k_slab_bucket; A/B)
-static int slab_chunks_override() {
-  static const int v = [] {
-    const char* e = ab_env("RPT_SLAB_CHUNKS");
-    return e ? std::atoi(e) : 0;
-  }();
-  return v;
-}
-
-// A/B switch with three values: 0 off, 1 the default rule, 2 forced on (the parity tests of the
-// A/B build run a path on inputs its default rule would not take it for)
-static int ab_mode(const char* name) {
-  const char* e = ab_env(name);
-  const int v = e ? std::atoi(e) : 1;
-  return (v == 0 || v == 2) ? v : 1;
-}
-// RPT_CELL_BOX_MIXED=0: 16 lanes for every cell's box (k_cell_box); 2: k_cell_box_mixed always
-static int cell_box_mixed() {
-  static const int v = ab_mode("RPT_CELL_BOX_MIXED");
-  return v;
-}
-// RPT_UNION_SNAP=0: no root snapshot before the listed union pass; 2: also on dense slabs
-static int union_snapshot() {
-  static const int v = ab_mode("RPT_UNION_SNAP");
-  return v;
-}
-
-// RPT_LABEL_ORIG=0: core labels scattered from sorted order (k_label_core); 2: the inverse
-// permutation and original-order labels at every density
-static int label_core_orig() {
-  static const int v = ab_mode("RPT_LABEL_ORIG");
-  return v;
-}
-
-// RPT_CELL_COMP=0: the per-point union init / component / core-label kernels also on grids whose
-// cells are all mutual (k_parent_init_cells, k_cell_comp, k_label_core_cells otherwise)
-static bool cell_comp_enabled() {
-  static const bool on = [] {
-    const char* e = ab_env("RPT_CELL_COMP");
-    return !(e && std::atoi(e) == 0);
-  }();
-  return on;
-}
-
-// RPT_CHUNK_SCAN=1: the one-block-per-slab k_slab_chunk_scan (A/B)
-static bool chunk_scan_legacy() {
-  static const bool v = [] {
-    const char* e = ab_env("RPT_CHUNK_SCAN");
-    return e && std::atoi(e) == 1;
-  }();
-  return v;
-}
 
 // occ_base[s] = the first occupied-list position of slab s (the flags' exclusive scan at the
 // slab's first cell), occ_base[nt] = the occupied count
@@ -979,21 +927,10 @@ __device__ __forceinline__ bool occupied(const uint32_t* __restrict__ bits, int6
 }
 
 // grids of the persistent wave-per-item kernels (item counts live on the device)
-// A/B build: RPT_WAVE_GRID_CAP caps the wave-per-item kernels' grids (fewer resident waves
-// leave room for other stacks' kernels on the same CUs)
-static int wave_grid_cap() {
-  static const int cap = [] {
-    const char* e = ab_env("RPT_WAVE_GRID_CAP");
-    const int v = e ? std::atoi(e) : 0;
-    return v >= 8 ? v : 4096;
-  }();
-  return cap;
-}
 inline int wave_grid(int64_t max_items) {  // a multiple of 8 blocks (XCD-aware ranges)
-  const int g = grid_for(max_items, kBlock / 64, wave_grid_cap());
+  const int g = grid_for(max_items, kBlock / 64, ab().wave_grid_cap);
   return (g + 7) & ~7;
 }
-constexpr int kDefaultUfFlags = 2;
 inline int tile_grid(int64_t n) { return grid_for(n, kBlock * 16, 2048); }
 
 __device__ __forceinline__ float wave_minf(float v) {
@@ -1765,14 +1702,6 @@ constexpr int kR = 4;  // candidate cells per lane per super-round of the window
 static_assert(kR >= 2, "the union passes' candidate masks cover two 64-position rounds");
 // k_union_cells: the top bit of a cell's candidate mask = "not recorded, enumerate the window"
 constexpr uint32_t kPmaskFull = 0x80000000u;
-// RPT_CELL_ROOTS=0: k_ccmin walks every core point's parent chain (A/B)
-static bool cell_roots_enabled() {
-  static const bool on = [] {
-    const char* e = ab_env("RPT_CELL_ROOTS");
-    return !(e && std::atoi(e) == 0);
-  }();
-  return on;
-}
 
 // Level 1, one thread per occupied cell: a mutual cell (every pair adjacent) holding >=
 // min_samples points is all core — the bulk of a radar stack.  Every other cell is queued for
@@ -4446,78 +4375,34 @@ struct DbscanState {
   uint32_t* occ_bits = nullptr;              // 1 bit per cell
   uint4* pmask = nullptr;  // union passes' undecided-candidate masks per occupied cell (aliases
                            // the grid build's radix key buffers, dead after the build)
-  int union_list = -1;     // RPT_UNION_LIST=0: the second union pass enumerates every window
-  int union_pair = -1;     // RPT_UNION_PAIR=0: one cell per wave in the box-certain union pass
-  int union_nm = -1;       // RPT_UNION_NM=0: k_union over every point (not the listed cells')
   // occupied cells per wave iteration of k_union_cells_pair: 64 on large stacks (one header load
-  // per lane), 16 on small ones (RPT_UNION_CPW in the A/B build)
+  // per lane), 16 on small ones (ab().union_cpw overrides)
   int union_cpw() const {
-    const char* e = ab_env("RPT_UNION_CPW");
-    const int v = e ? std::atoi(e) : 0;
-    if (v >= 1 && v <= 64) return v;
+    if (ab().union_cpw) return ab().union_cpw;
     return n > (int64_t(1) << 24) ? 64 : 16;
   }
-  int uf_compress = -1;    // RPT_UF_COMPRESS=1: a compression pass closes the union stage
   uint32_t* min_bits = nullptr;  // component minima, 1 bit per original index (MinRank)
   int32_t* min_pref = nullptr;   // exclusive popcount prefix of min_bits' words (+ total)
   int64_t min_words() const { return n / 32 + 1; }
   int32_t* n_clusters_ptr() const { return min_pref + min_words(); }
   int32_t cluster_ids(hipStream_t st, int32_t* cell_key, int32_t* zero = nullptr);
   int32_t* cell_root = nullptr;  // per cell: root of a mutual cell's core points (k_cell_roots)
-  int uf_flags = -1;                         // see XcdRange; -1 = read RPT_UF_FLAGS once
-  int k5_legacy = -1;                        // 1: round-1 K5 (fill + point queue); RPT_K5_MODE
-  int k5_fill = 0;
-  int k5_fused = -1;                         // 0: separate level-3 fill pass; RPT_K5_FUSED
   bool bucket_allmin = false;  // this build's cell minima came from k_slab_bucket
-  void k5_env() {
-    if (k5_legacy < 0) {  // RPT_K5_MODE: 0 round-1 queue pipeline, 1 cells write point flags,
-                          // 2 cells + point-flag fill (no queue); both 1/2 end in k_core_slow_cells
-      // default 0: the folded variants measured no faster on the 100- and 1000-frame stacks
-      // (profiles/r2/ab_k5_k1.md): the per-point flag writes moved into the cell kernel by 8 lanes
-      // per cell cost what the fill pass cost, and the cell-wise slow pass balances worse than the
-      // point queue
-      const char* e = ab_env("RPT_K5_MODE");
-      k5_legacy = e ? std::atoi(e) : 0;
-      k5_legacy = (k5_legacy == 0) ? 1 : 0;
-      k5_fill = (e && std::atoi(e) == 2) ? 1 : 0;
-    }
-    if (k5_tiles < 0) {  // RPT_K5_TILES=1: the LDS-tile pass (k_core_tiles; measured slower)
-      const char* e = ab_env("RPT_K5_TILES");
-      k5_tiles = (e && std::atoi(e) == 1) ? 1 : 0;
-    }
-    if (k5_fused < 0) {  // RPT_K5_FUSED=0: the separate level-3 fill pass (A/B)
-      const char* e = ab_env("RPT_K5_FUSED");
-      k5_fused = (e && std::atoi(e) == 0) ? 0 : 1;
-    }
-  }
   // the default K5 pipeline: the cell pass writes the point flags and the queue itself, with the
-  // all-core cells' minima from k_cell_box (decided at build time, before k_cell_box runs)
-  int k5_mask_ = -1;  // 0: the slow pass re-classifies every window (k_core_slow); RPT_K5_MASK
-  bool k5_mask() {
-    if (k5_mask_ < 0) {
-      const char* e = ab_env("RPT_K5_MASK");
-      k5_mask_ = (e && std::atoi(e) == 0) ? 0 : 1;
-    }
-    return k5_mask_ == 1;
+  // all-core cells' minima from k_cell_box (decided at build time, before k_cell_box runs).
+  // k5_mode 0 (the round-1 queue pipeline) is the default: the folded variants measured no faster
+  // on the 100- and 1000-frame stacks (profiles/r2/ab_k5_k1.md): the per-point flag writes moved
+  // into the cell kernel by 8 lanes per cell cost what the fill pass cost, and the cell-wise slow
+  // pass balances worse than the point queue
+  bool k5_fused_path() const {
+    return oct_ok() && ab().k5_mode == 0 && ab().k5_fused && !ab().k5_tiles;
   }
-  bool k5_fused_path() {
-    k5_env();
-    return oct_ok() && k5_legacy && k5_fused && !k5_tiles;
-  }
-  int k5_tiles = -1;                         // 1: K5 by LDS tiles (k_core_tiles); RPT_K5_TILES
-  int k7_tiles = -1;                         // 1: K7 by LDS tiles (k_label_tiles); RPT_K7_TILES
   int32_t* rowq = nullptr;    // first occupied-list index of every (slab, row) + total (tiles)
   int32_t* rowcnt = nullptr;  // occupied cells per (slab, row)
   bool rowq_ok = false;       // rowq built for this grid (the core pass's tile path)
   int tile_by = 0, tile_nbands = 0, tile_R = 0;
-  // the label pass on the core pass's tiles (rowq built, RPT_K7_TILES not 0)
-  bool use_label_tiles() {
-    if (k7_tiles < 0) {  // RPT_K7_TILES=1 (measured slower than k_label, see k_core_tiles)
-      const char* e = ab_env("RPT_K7_TILES");
-      k7_tiles = (e && std::atoi(e) == 1) ? 1 : 0;
-    }
-    return k7_tiles && rowq_ok && dim == 2 && g.nz == 1;
-  }
+  // the label pass on the core pass's tiles (rowq built, ab().k7_tiles on)
+  bool use_label_tiles() const { return ab().k7_tiles && rowq_ok && dim == 2 && g.nz == 1; }
   unsigned tile_grid_blocks() const {  // the tiles + the isolated cell's, a multiple of 8
     return (unsigned)((((int64_t)g.nt * tile_nbands + 1) + 7) & ~(int64_t)7);
   }
@@ -4530,15 +4415,6 @@ struct DbscanState {
   }
   // the eight-lanes-per-cell K5 / K6 kernels (2-D, at most kCwMaxR slabs each side)
   bool oct_ok() const { return dim == 2 && g.nz == 1 && slab_reach() <= (double)kCwMaxR; }
-  int k7_w = -1;  // lanes per non-core point in k_label (32: two points per wave); RPT_K7_W
-  int label_w() {
-    if (k7_w < 0) {
-      const char* e = ab_env("RPT_K7_W");
-      k7_w = (e && std::atoi(e) == 64) ? 64 : 32;
-    }
-    return k7_w;
-  }
-  int bucket_mode = -1;                      // RPT_K4_BUCKET (default 1): slab-bucket K4
   template <int D>
   const CellRec<D>* rec() const {
     return static_cast<const CellRec<D>*>(crec);
@@ -4560,30 +4436,11 @@ struct DbscanState {
   // fused local path with a readback of the cluster count; set by union_pass, read by
   // labels_local)
   bool cell_comp = false;
-  // the union passes' A/B switches (read once)
-  void union_env() {
-    if (union_list < 0) {
-      const char* e = ab_env("RPT_UNION_LIST");
-      union_list = (e && std::atoi(e) == 0) ? 0 : 1;
-    }
-    if (union_pair < 0) {
-      const char* e = ab_env("RPT_UNION_PAIR");
-      union_pair = (e && std::atoi(e) == 0) ? 0 : 1;
-    }
-    if (union_nm < 0) {
-      const char* e = ab_env("RPT_UNION_NM");
-      union_nm = (e && std::atoi(e) == 0) ? 0 : 1;
-    }
-    if (uf_compress < 0) {
-      const char* e = ab_env("RPT_UF_COMPRESS");
-      uf_compress = (e && std::atoi(e) == 1) ? 1 : 0;
-    }
-  }
   // a fused local run on this grid takes the per-cell path (cell_comp; see union_pass)
-  bool cell_comp_ok() {
-    union_env();
-    return all_mutual && dim == 2 && union_list && union_pair && union_nm &&
-           cell_comp_enabled() && !use_label_tiles() && !uf_compress;
+  bool cell_comp_ok() const {
+    const AbSwitches& a = ab();
+    return all_mutual && dim == 2 && a.union_list && a.union_pair && a.union_nm && a.cell_comp &&
+           !use_label_tiles() && !a.uf_compress;
   }
   // The sorted points are float2 {x, y} in the first half of pts' allocation (Pt<true>), not
   // float4: the build's writer was k_slab_bucket<true> / k_slab_chunk_scatter<true>.  A kernel
@@ -4600,16 +4457,12 @@ struct DbscanState {
   // K5 pipelines (RPT_K5_MODE / _TILES / _FUSED / _MASK, eps_t >= 3), the per-point union paths
   // (RPT_UNION_PAIR / _LIST / _NM, RPT_CELL_COMP=0, RPT_UF_COMPRESS=1), the label tiles and the
   // 64-lane label pass (RPT_K7_TILES, RPT_K7_W=64).  RPT_XY_POINTS=0 keeps float4 (A/B).
-  bool xy_rule() {
-    static const bool on = [] {
-      const char* e = ab_env("RPT_XY_POINTS");
-      return !(e && std::atoi(e) == 0);
-    }();
-    (void)use_label_tiles();  // (reads RPT_K7_TILES)
+  bool xy_rule() const {
+    const AbSwitches& a = ab();
     // (a fractional eps_t also keeps float4: its windows are tfree all the same, it is only
     // not among the cases the layout was measured and tested on)
-    return on && dim == 2 && g.tfree && g.epst == std::floor(g.epst) && cell_comp_ok() &&
-           k5_fused_path() && (int)slab_reach() <= 2 && k5_mask() && !k7_tiles && label_w() == 32;
+    return a.xy_points && dim == 2 && g.tfree && g.epst == std::floor(g.epst) && cell_comp_ok() &&
+           k5_fused_path() && (int)slab_reach() <= 2 && a.k5_mask && !a.k7_tiles && a.k7_w == 32;
   }
   int32_t need_float4(const char* who) const {
     if (!xy_points) return RPT_OK;
@@ -4675,11 +4528,7 @@ int32_t DbscanState::build_t(const float* x, const float* y, const float* z, int
   g = Geom{};
   g.eps2 = eps_space * eps_space;
   g.epst = epst;
-  static const bool screen_on = [] {
-    const char* e = ab_env("RPT_F32_SCREEN");
-    return !(e && e[0] == '0');
-  }();
-  const bool screen = screen_on && g.eps2 >= 1e-20 && g.eps2 <= 1e30;
+  const bool screen = ab().f32_screen && g.eps2 >= 1e-20 && g.eps2 <= 1e30;
   g.e2lo = screen ? (float)(g.eps2 * (1.0 - 1e-5)) : -1.0f;
   g.e2hi = screen ? (float)(g.eps2 * (1.0 + 1e-5)) : INFINITY;
   g.min_samples = min_samples;
@@ -4694,13 +4543,8 @@ int32_t DbscanState::build_t(const float* x, const float* y, const float* z, int
   // cell side: >= eps/2 keeps every neighbour within +-2 cells; in 2-D up to eps/sqrt(2) keeps a
   // full cell's diagonal within eps (mutual cells possible), and larger cells hold more points,
   // so more of them are decided whole: 0.7 eps in 2-D (1000-frame stack 12.86 -> 12.41 ms, the
-  // dense share's K5 0.66 -> 0.84 of roofline, same box); RPT_CELL_SIDE overrides (0.5 - 0.7)
-  static const double side_f = [] {
-    const char* e = ab_env("RPT_CELL_SIDE");
-    const double v = e ? std::atof(e) : 0.0;
-    return (v >= 0.5 && v <= 0.7) ? v : 0.7;
-  }();
-  const double sf = (D == 2) ? side_f : 0.5;
+  // dense share's K5 0.66 -> 0.84 of roofline, same box); ab().cell_side overrides (0.5 - 0.7)
+  const double sf = (D == 2) ? ab().cell_side : 0.5;
   double cs = (eps_space > 0.0 ? eps_space * sf : 1.0) * margin;
   double ct = !hb.nonintegral_t ? 1.0 : (epst > 0.f ? (double)epst : 1.0) * margin;
   const int64_t cmax = std::min<int64_t>(std::max<int64_t>(int64_t(1) << 22, 4 * n),
@@ -4826,13 +4670,9 @@ int32_t DbscanState::build_t(const float* x, const float* y, const float* z, int
     set_error("internal: scratch carve overflow");
     return RPT_ENOMEM;
   }
-  if (bucket_mode < 0) {
-    const char* e = ab_env("RPT_K4_BUCKET");
-    bucket_mode = (e && std::atoi(e) == 0) ? 0 : 1;
-  }
   // time-ordered finite 2-D points with a slab's cells fitting LDS: per-slab counting sort
   bucket_allmin = false;
-  const bool bucket = bucket_mode && D == 2 && hb.n_finite_t == n && !hb.t_descends &&
+  const bool bucket = ab().k4_bucket && D == 2 && hb.n_finite_t == n && !hb.t_descends &&
                       (int64_t)nx * ny <= kBucketCells && nt < (int64_t(1) << 31);
   // xy points: written by the slab writers only, every time finite (no isolated cell)
   xy_points = may_xy && bucket && D == 2 && hb.n_finite_t == n && xy_rule();
@@ -4853,15 +4693,15 @@ int32_t DbscanState::build_t(const float* x, const float* y, const float* z, int
     // permutation written here (configs[4] share: 676 -> 253 us for +57 in the scatter; at
     // standard density the scattered writes stay in L2 and the extra store costs +68 us)
     dense_slabs = avg > 8 * kChunkPts;
-    spos_on = label_core_orig() == 2 || (label_core_orig() == 1 && dense_slabs);
+    spos_on = ab().label_orig == 2 || (ab().label_orig == 1 && dense_slabs);
     int32_t* spos_w = spos_on ? slab : nullptr;
     int64_t ch = avg > 8 * kChunkPts ? (avg + kChunkPts - 1) / kChunkPts : 1;
     ch = std::max<int64_t>(ch, (512 + nt - 1) / std::max<int64_t>(nt, 1));
     int CH = (int)std::min<int64_t>(ch, 64);
     while (CH > 1 && (int64_t)nt * CH * nx * ny > 4 * n) --CH;
-    if (slab_chunks_override() > 0) CH = slab_chunks_override();
+    if (ab().slab_chunks > 0) CH = ab().slab_chunks;
     const bool coalesced_scan = CH >= 8 && (int64_t)nt * CH * nx * ny <= 4 * n &&
-                                !chunk_scan_legacy();
+                                !ab().chunk_scan;
     if (CH > 1 && (int64_t)nt * CH * nx * ny <= 4 * n) {
       int32_t* hist_g = reinterpret_cast<int32_t*>(keys);
       // the coalesced passes pay for their extra launches only with many chunks per slab (dense
@@ -4907,13 +4747,13 @@ int32_t DbscanState::build_t(const float* x, const float* y, const float* z, int
     } else {
       // the fused K5's all-core cell minima from the counting sort when both LDS arrays fit 64 KiB
       bucket_allmin = k5_fused_path() && 2 * hist_bytes <= 65536 &&
-                      ab_mode("RPT_BUCKET_ALLMIN") != 0;  // (=0: from k_cell_box; A/B)
+                      ab().bucket_allmin != 0;  // (=0: from k_cell_box; A/B)
       const size_t lds = bucket_allmin ? 2 * hist_bytes : hist_bytes;
       RPT_HIP(hipFuncSetAttribute(xy_points ? (const void*)k_slab_bucket<true>
                                             : (const void*)k_slab_bucket<false>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 #ifdef RPT_AB
-      if (ab_env("RPT_STATS")) {  // A/B diagnostics: blocks per CU the runtime admits
+      if (ab().stats) {  // A/B diagnostics: blocks per CU the runtime admits
         int nb = -1;
         if (xy_points)
           (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_slab_bucket<true>,
@@ -4955,7 +4795,7 @@ int32_t DbscanState::build_t(const float* x, const float* y, const float* z, int
     uint32_t *sk, *sv;
     RPT_TRY(radix_sort_pairs(keys, vals, keys_alt, vals_alt, n, bits, rtmp, &sk, &sv, st));
     dense_slabs = false;
-    spos_on = label_core_orig() == 2;
+    spos_on = ab().label_orig == 2;
     hipLaunchKernelGGL(k_gather<D>, dim3(gb), dim3(kBlock), 0, st, x, y, z, stride, t, n, sk, sv,
                        pts, sorig, skey, spos_on ? slab : nullptr);
     RPT_HIP(hipMemsetAsync(cell_start, 0, sizeof(int32_t) * C1, st));
@@ -4975,8 +4815,8 @@ int32_t DbscanState::build_t(const float* x, const float* y, const float* z, int
     // the 125-frame share has too few 64-cell waves to fill the GPU (48 -> 60 us) and dense
     // slabs' cells are large (324 -> 402 us): 16 lanes for every cell there
     // (RPT_CELL_BOX_MIXED=0 in the A/B build: always)
-    const bool mixed = cell_box_mixed() == 2 ||
-                       (cell_box_mixed() == 1 && !dense_slabs && n > (int64_t(1) << 24));
+    const bool mixed = ab().cell_box_mixed == 2 ||
+                       (ab().cell_box_mixed == 1 && !dense_slabs && n > (int64_t(1) << 24));
     const dim3 gm(grid_for(n, kBlock, 4096)), gl(grid_for(kCbLanes * n, kBlock, 8192));
     if (xy_points) {
       if constexpr (D == 2) {  // (the records' time fields from slab_t, written above)
@@ -5034,12 +4874,11 @@ int32_t DbscanState::core_pass(hipStream_t st) {
   int32_t* slow = nc_list;
   int32_t* n_slow = nc_list + n;
   const int32_t* n_occ = n_occ_dev;
-  k5_env();
   const double rs = slab_reach();
   const bool oct = oct_ok();
   if (!k5_fused_path()) RPT_TRY(need_float4("core_pass"));
 #ifdef RPT_AB  // A/B-only forms (stdbscan_ab.inc)
-  if (oct && k5_tiles) {
+  if (oct && ab().k5_tiles) {
     // LDS tiles: band height BY with the map (W slabs x BY + 4 rows x nx) and the undecided list
     // (BY x nx own cells) within their LDS arrays; rowq (kept for the label pass's tiles)
     const int R = (int)rs, W = 2 * R + 1;
@@ -5064,7 +4903,8 @@ int32_t DbscanState::core_pass(hipStream_t st) {
       return RPT_OK;
     }
   }
-  if (!k5_legacy) {
+  if (ab().k5_mode != 0) {
+    const bool k5_fill = ab().k5_mode == 2;  // (no queue: the cells' point flags by a fill pass)
     // cells decide (and write their points' flags) in one pass; the undecided cells' points are
     // settled by k_core_slow_cells, which walks the occupied cells itself (no queue, no fill)
     if (oct) {
@@ -5106,7 +4946,7 @@ int32_t DbscanState::core_pass(hipStream_t st) {
     // the cell pass's decisions handed to the slow pass when its window's 5 W (slab, row) pairs
     // x 5 columns fit a 128-bit mask (W <= 5; pmask / clo per occupied cell in the dead radix
     // buffers / cid, both rebuilt later)
-    const bool masked = (int)rs <= 2 && k5_mask();
+    const bool masked = (int)rs <= 2 && ab().k5_mask;
     if (!masked) RPT_TRY(need_float4("core_pass"));
     uint4* k5m = reinterpret_cast<uint4*>(pmask);
     if (masked) {
@@ -5139,7 +4979,7 @@ int32_t DbscanState::core_pass(hipStream_t st) {
     RPT_CHECK_LAUNCH();
     cmin_ready = true;
 #ifdef RPT_AB
-    if (ab_env("RPT_STATS")) {  // A/B diagnostics: K5's slow queue and its cells (syncs)
+    if (ab().stats) {  // A/B diagnostics: K5's slow queue and its cells (syncs)
       int32_t h = 0;
       (void)hipMemcpyAsync(&h, n_slow, 4, hipMemcpyDeviceToHost, st);
       (void)hipStreamSynchronize(st);
@@ -5192,10 +5032,8 @@ int32_t DbscanState::core_pass(hipStream_t st) {
 int32_t DbscanState::union_pass(hipStream_t st, bool fused) {
   cell_comp = false;
   if (degenerate) return RPT_OK;
-  if (uf_flags < 0) {
-    const char* e = ab_env("RPT_UF_FLAGS");
-    uf_flags = e ? (std::atoi(e) & 3) : kDefaultUfFlags;
-  }
+  const AbSwitches& a = ab();
+  const int uf_flags = a.uf_flags;  // see XcdRange
   const int gb = grid_for(n, kBlock, 2048);
   const int gc = grid_for(C, kBlock, 8192);
   const int gw = wave_grid(n);
@@ -5204,16 +5042,15 @@ int32_t DbscanState::union_pass(hipStream_t st, bool fused) {
   (void)gc;
   // per-cell (min original index, sorted index) of the core points, one u64 per cell
   auto* cmin = reinterpret_cast<unsigned long long*>(cell_min_pair);
-  union_env();
   // 2-D: the first union pass lists its cells with undecided candidates in nc_list (free until
   // the label pass), their count at nc_list[n] (zeroed by k_init_occ_cells)
-  const bool listing = union_list && dim == 2;
+  const bool listing = a.union_list && dim == 2;
   int32_t* plist = listing ? nc_list : nullptr;
   int32_t* pcount = listing ? nc_list + n : nullptr;
   // 2-D pair path: the non-mutual cells with core points listed by the first pass in cid (free
   // until the label pass), their count at cid[n]; k_union_nm then takes only their points
   // (RPT_UNION_NM=0 in the A/B build: k_union over every point)
-  const bool nm = dim == 2 && union_pair && union_nm;
+  const bool nm = dim == 2 && a.union_pair && a.union_nm;
   int32_t* nm_list = nm ? cid : nullptr;
   int32_t* nm_count = nm ? cid + n : nullptr;
   // all_mutual grids on the default 2-D pair path: only the cell representatives' parent
@@ -5241,7 +5078,7 @@ int32_t DbscanState::union_pass(hipStream_t st, bool fused) {
   int32_t* lstat_dev = nullptr;  // (A/B diagnostics)
   if (dim == 2) {
     uint4* pm = listing ? pmask : nullptr;
-    if (union_pair)  // two cells per wave (RPT_UNION_PAIR=0 in the A/B build: one)
+    if (a.union_pair)  // two cells per wave (RPT_UNION_PAIR=0 in the A/B build: one)
       hipLaunchKernelGGL(k_union_cells_pair, dim3(gw), dim3(kBlock), 0, st, pts, g, occ, n_occ,
                          rec<2>(), occ_bits, slab_t, rep, mutual, sorig, parent, uf_flags, pm,
                          plist, pcount, union_cpw(), nm_list, nm_count);
@@ -5250,7 +5087,7 @@ int32_t DbscanState::union_pass(hipStream_t st, bool fused) {
                          cell_start, occ, n_occ, rec<2>(), occ_bits, slab_t, core, rep, mutual,
                          sorig, parent, uf_flags, pm, plist, pcount);
 #ifdef RPT_AB
-    if (listing && ab_env("RPT_STATS")) {  // (A/B diagnostics: a leaked 16 B per process)
+    if (listing && ab().stats) {  // (A/B diagnostics: a leaked 16 B per process)
       static int32_t* buf = nullptr;
       if (!buf) (void)hipMalloc(&buf, 16);
       lstat_dev = buf;
@@ -5261,7 +5098,7 @@ int32_t DbscanState::union_pass(hipStream_t st, bool fused) {
       // the snapshot in cell_root (free until the label stage's k_cell_roots); not on dense
       // slabs, where it measured slower (configs[4] share: +38 us snapshot, listed 867 -> 916 us;
       // 1000 standard frames: listed 348 -> 202 us for +28)
-      const bool snap = union_snapshot() == 2 || (union_snapshot() == 1 && !dense_slabs);
+      const bool snap = ab().union_snap == 2 || (ab().union_snap == 1 && !dense_slabs);
       if (snap)
         hipLaunchKernelGGL(k_cell_root_snapshot, dim3(grid_for(n, kBlock, 4096)), dim3(kBlock),
                            0, st, occ, n_occ, rep, parent, g.cells, uf_flags, cell_root);
@@ -5303,10 +5140,10 @@ int32_t DbscanState::union_pass(hipStream_t st, bool fused) {
   // separate compression pass only moves that work; RPT_UF_COMPRESS=1 keeps it (A/B; read
   // above: it rules the per-cell init out)
 #ifdef RPT_AB
-  if (uf_compress && !cell_comp)
+  if (a.uf_compress && !cell_comp)
     hipLaunchKernelGGL(k_compress, dim3(gb), dim3(kBlock), 0, st, parent, core, n, sorig,
                        (int32_t*)nullptr);
-  if (ab_env("RPT_STATS")) {  // A/B diagnostics: the queue and list sizes of this run (syncs)
+  if (ab().stats) {  // A/B diagnostics: the queue and list sizes of this run (syncs)
     int32_t h[2] = {0, 0}, ls[4] = {0, 0, 0, 0};
     (void)hipMemcpyAsync(&h[0], n_occ_dev, 4, hipMemcpyDeviceToHost, st);
     if (listing) (void)hipMemcpyAsync(&h[1], pcount, 4, hipMemcpyDeviceToHost, st);
@@ -5333,7 +5170,7 @@ int32_t DbscanState::cluster_ids(hipStream_t st, int32_t* cell_key, int32_t* zer
   // per-cell roots of the mutual cells (read by k_ccmin for their core points); zero (nullable):
   // k_ccmin's non-core queue counter, cleared by k_cell_roots, which also clears the minimum
   // bits and fills cell_key (nullable) with INT_MAX (one launch instead of three)
-  const bool cr = cell_roots_enabled();
+  const bool cr = ab().cell_roots;
   if (cr) {
     hipLaunchKernelGGL(k_cell_roots, dim3(grid_for(n, kBlock, 2048)), dim3(kBlock), 0, st, parent,
                        occ, n_occ_dev, C, mutual, rep, cell_root, zero, min_bits, W, cell_key);
@@ -5399,10 +5236,10 @@ int32_t DbscanState::labels_local(int32_t* labels, rpt_stdbscan_stats* stats, hi
       hipLaunchKernelGGL(k_label_core, dim3(glc), dim3(kBlock), 0, st, ccmin, n, sorig, mr,
                          labels);
   }
-  if (!cell_comp || label_w() != 32 || use_label_tiles()) RPT_TRY(need_float4("labels_local"));
+  if (!cell_comp || ab().k7_w != 32 || use_label_tiles()) RPT_TRY(need_float4("labels_local"));
   int32_t* kstat = nullptr;  // (A/B diagnostics)
 #ifdef RPT_AB
-  if (ab_env("RPT_STATS")) {  // (a leaked 16 B per process)
+  if (ab().stats) {  // (a leaked 16 B per process)
     static int32_t* buf = nullptr;
     if (!buf) (void)hipMalloc(&buf, 16);
     kstat = buf;
@@ -5415,12 +5252,12 @@ int32_t DbscanState::labels_local(int32_t* labels, rpt_stdbscan_stats* stats, hi
                        g, tile_R, tile_by, tile_nbands, (int64_t)g.nt * tile_nbands, occ,
                        n_occ_dev, rowq, rec<2>(), mutual, occ_bits, slab_t, pts, ccmin, cell_min,
                        sorig, mr, min_samples, labels);
-  else if (cell_comp && label_w() == 64)
+  else if (cell_comp && ab().k7_w == 64)
     hipLaunchKernelGGL((k_label<2, false, 64, true>), dim3(wave_grid(n)), dim3(kBlock), 0, st,
                        pts, skey, g, rec<2>(), occ_bits, slab_t, (const int32_t*)nullptr,
                        cell_min, mutual, sorig, mr, nc_list, nc_count, labels,
                        (int32_t*)nullptr, core);
-  else if (dim == 2 && label_w() == 64)
+  else if (dim == 2 && ab().k7_w == 64)
     hipLaunchKernelGGL((k_label<2, false, 64>), dim3(wave_grid(n)), dim3(kBlock), 0, st, pts,
                        skey, g, rec<2>(), occ_bits, slab_t, ccmin, cell_min, mutual, sorig, mr,
                        nc_list, nc_count, labels);
@@ -5502,7 +5339,7 @@ int32_t DbscanState::labels_global(const int64_t* rep_orig, const int64_t* reps,
   RPT_TRY(need_float4("labels_global"));
   const int gb = grid_for(n, kBlock, 2048);
   int32_t* nc_count = nc_list + n;
-  const bool cr = cell_roots_enabled();
+  const bool cr = ab().cell_roots;
   if (cr) {  // (also clears nc_count for k_ccmin_global and fills cell_min with INT_MAX)
     hipLaunchKernelGGL(k_cell_roots, dim3(grid_for(n, kBlock, 2048)), dim3(kBlock), 0, st, parent,
                        occ, n_occ_dev, C, mutual, rep, cell_root, nc_count, (uint32_t*)nullptr,
@@ -5534,7 +5371,7 @@ int32_t DbscanState::labels_global(const int64_t* rep_orig, const int64_t* reps,
                        g, tile_R, tile_by, tile_nbands, (int64_t)g.nt * tile_nbands, occ,
                        n_occ_dev, rowq, rec<2>(), mutual, occ_bits, slab_t, pts, slab, cell_min,
                        sorig, MinRank{nullptr, nullptr}, min_samples, labels);
-  else if (dim == 2 && label_w() == 64)
+  else if (dim == 2 && ab().k7_w == 64)
     hipLaunchKernelGGL((k_label<2, true, 64>), dim3(wave_grid(n)), dim3(kBlock), 0, st, pts,
                        skey, g, rec<2>(), occ_bits, slab_t, slab, cell_min, mutual, sorig,
                        MinRank{nullptr, nullptr}, nc_list, nc_count, labels);

@@ -1268,13 +1268,9 @@ static int32_t summaries_impl(const int32_t* labels, const float* x, const float
     return RPT_OK;
   };
   const int64_t sh = std::max<int64_t>(1, std::min<int64_t>(s_hint, n));
-  // per-frame counting sort unless forced off (RPT_K9_RADIX=1, or a redo after a frame held more
+  // per-frame counting sort unless forced off (ab().k9_radix, or a redo after a frame held more
   // than kFsMaxKeys labels) or frames are huge (one 8-wave block per frame)
-  static const bool env_radix = [] {
-    const char* e = ab_env("RPT_K9_RADIX");
-    return e && e[0] == '1';
-  }();
-  const bool frame_sort = !force_radix && !env_radix && n_frames > 0 && n > 0 &&
+  const bool frame_sort = !force_radix && !ab().k9_radix && n_frames > 0 && n > 0 &&
                           n / n_frames <= (int64_t(1) << 20);
   if (radix_used) *radix_used = !frame_sort;
   if (frame_sort) {

@@ -10,7 +10,7 @@ separately rounded float operations.
 
 ``build(ab=True)`` (``python -m rpt._build --ab``) compiles the same sources with ``-DRPT_AB``
 into ``rpt/librpt_ab.so`` (objects under ``build_ab/``): the only build whose kernels read the
-``RPT_*`` A/B switches from the environment (csrc/common.h ``ab_env``).  ``tools/ab_*.sh`` load it
+``RPT_*`` A/B switches from the environment (csrc/ab_switches.h ``ab()``).  ``tools/ab_*.sh`` load it
 through ``RPT_LIB``; the shipped ``librpt.so`` ignores the environment.
 """
 from __future__ import annotations

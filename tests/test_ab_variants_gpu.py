@@ -1,8 +1,12 @@
 """Every kernel form the A/B build keeps selectable (librpt_ab.so, the only build that reads the
-RPT_* switches; tools/ab_*.sh measure with it) must give the shipped library's results: three child
+RPT_* switches; tools/ab_*.sh measure with it) must give the shipped library's results: child
 processes, each with a set of switches at non-default values, run the same 14-frame stack (land
 filter on) and return labels, per-(frame, label) rows, K1 points and tracks, compared bit for bit
-with librpt.so's run in this process.  Together the sets flip every switch the A/B build reads."""
+with librpt.so's run in this process.  Together with the RPT_XY_POINTS, RPT_CELL_COMP and
+RPT_CHUNK_SCAN cases of test_xy_points_gpu.py (whose children run under RPT_STATS), the
+RPT_K5_FUSED case of test_bigstack_gpu.py and the RPT_K9_RADIX cases of test_path_gpu.py, the sets
+flip every switch the A/B build reads (csrc/ab_switches.h; tests/test_ab_switches_host.py holds
+the tests' sets against the table)."""
 from __future__ import annotations
 
 import os
@@ -28,6 +32,12 @@ COMBOS = [
     # root snapshot before the listed union pass, k_union over every point
     {"RPT_CELL_BOX_MIXED": "2", "RPT_LABEL_ORIG": "2", "RPT_UNION_SNAP": "0",
      "RPT_UNION_NM": "0"},
+    # the slow pass without the cell pass's masks (k_core_slow), 64 cells per wave iteration of
+    # k_union_cells_pair, the wave-per-item grids capped at 64 blocks, and one block per slab
+    # (k_slab_bucket, where the all-core cell minima's source is chosen) with the minima from
+    # k_cell_box
+    {"RPT_K5_MASK": "0", "RPT_UNION_CPW": "64", "RPT_WAVE_GRID_CAP": "64", "RPT_SLAB_CHUNKS": "1",
+     "RPT_BUCKET_ALLMIN": "0"},
 ]
 
 RUN = r'''

@@ -201,17 +201,31 @@ def _run_children(switch):
 # (switches, xy_points expected on the eligible clouds)
 CHILD_CASES = [({}, 1), ({"RPT_XY_POINTS": "0"}, 0),
                ({"RPT_SLAB_CHUNKS": "1", "RPT_CELL_BOX_MIXED": "2"}, 1),
-               ({"RPT_CELL_BOX_MIXED": "0"}, 1)]
+               ({"RPT_CELL_BOX_MIXED": "0"}, 1),
+               # the one-block-per-slab chunk scan where the coalesced scan is the default: the
+               # "cells" cloud (3 frames, 6 x 1 cells: 64 chunks per slab); "slabs8" takes 2
+               # chunks and "slabs520" one block, below the coalesced scan's 8
+               ({"RPT_CHUNK_SCAN": "1"}, 1)]
 ELIGIBLE = ("cells", "slabs520", "slabs8")
 
 
+def _coalesced_scan(xy, t):
+    """build_t's rule for the coalesced chunk scan: CH >= 8 and nt * CH * nx * ny <= 4 n (the
+    second holds for every CH > 1 that _writer_chunks returns)."""
+    return _writer_chunks(xy, t) >= 8
+
+
 @pytest.mark.parametrize("switch,xy", CHILD_CASES,
-                         ids=["defaults", "xy_off", "one_block_mixed_box", "lanes_box"])
+                         ids=["defaults", "xy_off", "one_block_mixed_box", "lanes_box",
+                              "chunk_scan"])
 def test_children_over_the_clouds(gpu, shipped_labels, switch, xy):
     """Both writers (RPT_SLAB_CHUNKS=1: k_slab_bucket for every cloud; default: the chunked
     scatter for the short stacks) and both box kernels (RPT_CELL_BOX_MIXED=2: the one-lane small
     cells at <= kCbSmall = 4 points; 0 / default at this size: 16 lanes per cell), the layout
     each run reports, and labels equal to librpt.so's."""
+    if "RPT_CHUNK_SCAN" in switch:
+        scans = {k: _coalesced_scan(xy, t) for k, (xy, t, _) in _clouds().items() if k in ELIGIBLE}
+        assert scans == {"cells": True, "slabs520": False, "slabs8": False}, scans
     res = _run_children(switch)
     assert sorted(res) == sorted(shipped_labels)
     for k, (lab, lines) in res.items():
