@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "frame_index.h"
 
 #pragma clang fp contract(off)
 
@@ -168,14 +169,18 @@ __device__ __forceinline__ Edges stage_edges(const double* xe, int nxe, const do
 // per 256-thread block of a larger grid, and 16 waves per CU hide the LDS atomics' latency.
 constexpr int kLdsGridCells = 10240;
 constexpr int kGridBlock = 1024;
+// CT (all three grid kernels): the element type of cell_out, int32_t or -- the stack driver's
+// narrow path, grids of at most 65,536 cells -- uint16_t; VT: the element type of val, float
+// or -- the narrow path's u8 samples -- uint8_t
+template <class CT, class VT>
 __global__ __launch_bounds__(kGridBlock) void k_land_grid_lds(const float* __restrict__ x,
                                                          const float* __restrict__ y,
-                                                         const float* __restrict__ val, int64_t n,
+                                                         const VT* __restrict__ val, int64_t n,
                                                          const double* __restrict__ xe, int nxe,
                                                          const double* __restrict__ ye, int nye,
                                                          int32_t* __restrict__ cnt,
                                                          double* __restrict__ tot,
-                                                         int32_t* __restrict__ cell_out) {
+                                                         CT* __restrict__ cell_out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   double* lds_e = reinterpret_cast<double*>(smem);                    // nxe + nye edges
   const int ne = nxe + nye;
@@ -199,7 +204,7 @@ __global__ __launch_bounds__(kGridBlock) void k_land_grid_lds(const float* __res
     const int ix = clip_idx(count_le_arith(ex, nxe, (double)x[i], idx_) - 1, nxe - 2);
     const int iy = clip_idx(count_le_arith(ey, nye, (double)y[i], idy_) - 1, nye - 2);
     const int c = ix * ny + iy;
-    if (cell_out) cell_out[i] = c;
+    if (cell_out) cell_out[i] = (CT)c;
     atomicAdd(lds_c + c, 1);
     atomicAdd(lds_t + c, (double)val[i]);
   }
@@ -218,10 +223,11 @@ __global__ __launch_bounds__(kGridBlock) void k_land_grid_lds(const float* __res
 // the caller), instead of an int32 and a float64 atomic.  Integer sums below 2^53 are exact in any
 // order, so the float64 grid equals the unpacked kernel's.
 constexpr int kPackShift = 40;
+template <class CT, class VT>
 __global__ __launch_bounds__(kGridBlock) void k_land_grid_lds_u8(
-    const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ val,
+    const float* __restrict__ x, const float* __restrict__ y, const VT* __restrict__ val,
     int64_t n, const double* __restrict__ xe, int nxe, const double* __restrict__ ye, int nye,
-    int32_t* __restrict__ cnt, double* __restrict__ tot, int32_t* __restrict__ cell_out) {
+    int32_t* __restrict__ cnt, double* __restrict__ tot, CT* __restrict__ cell_out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   double* lds_e = reinterpret_cast<double*>(smem);  // nxe + nye edges
   const int ne = nxe + nye;
@@ -241,7 +247,8 @@ __global__ __launch_bounds__(kGridBlock) void k_land_grid_lds_u8(
   constexpr int kU = 8;
   const int64_t chunk = (int64_t)kGridBlock * kU;
   for (int64_t b0 = (int64_t)blockIdx.x * chunk; b0 < n; b0 += (int64_t)gridDim.x * chunk) {
-    float px[kU], py[kU], pv[kU];
+    float px[kU], py[kU];
+    VT pv[kU];
 #pragma unroll
     for (int k = 0; k < kU; ++k) {
       const int64_t i = min(b0 + (int64_t)k * kGridBlock + threadIdx.x, n - 1);  // branch-free
@@ -256,7 +263,7 @@ __global__ __launch_bounds__(kGridBlock) void k_land_grid_lds_u8(
       const int ix = clip_idx(count_le_arith(ex, nxe, (double)px[k], idx_) - 1, nxe - 2);
       const int iy = clip_idx(count_le_arith(ey, nye, (double)py[k], idy_) - 1, nye - 2);
       const int c = ix * ny + iy;
-      if (cell_out) cell_out[i] = c;
+      if (cell_out) cell_out[i] = (CT)c;
       atomicAdd(lds_p + c, (1ull << kPackShift) | (unsigned long long)(uint32_t)pv[k]);
     }
   }
@@ -270,14 +277,15 @@ __global__ __launch_bounds__(kGridBlock) void k_land_grid_lds_u8(
   }
 }
 
+template <class CT, class VT>
 __global__ __launch_bounds__(kBlock) void k_land_grid(const float* __restrict__ x,
                                                      const float* __restrict__ y,
-                                                     const float* __restrict__ val, int64_t n,
+                                                     const VT* __restrict__ val, int64_t n,
                                                      const double* __restrict__ xe, int nxe,
                                                      const double* __restrict__ ye, int nye,
                                                      int32_t* __restrict__ cnt,
                                                      double* __restrict__ tot,
-                                                     int32_t* __restrict__ cell_out) {
+                                                     CT* __restrict__ cell_out) {
   __shared__ double lds[kMaxEdges];
   const Edges E = stage_edges(xe, nxe, ye, nye, lds);
   const int ny = nye - 1;
@@ -286,7 +294,7 @@ __global__ __launch_bounds__(kBlock) void k_land_grid(const float* __restrict__ 
     const int ix = clip_idx(count_le(E.xe, nxe, (double)x[i]) - 1, nxe - 2);
     const int iy = clip_idx(count_le(E.ye, nye, (double)y[i]) - 1, nye - 2);
     const int64_t c = (int64_t)ix * ny + iy;
-    if (cell_out) cell_out[i] = (int32_t)c;
+    if (cell_out) cell_out[i] = (CT)c;
     atomicAdd(cnt + c, 1);
     atomicAdd(tot + c, (double)val[i]);
   }
@@ -379,21 +387,38 @@ struct BoundsPart {
   int32_t mnf, mxf, flags, pad;  // flags: 1 non-finite x/y, 2 frame slots descend
 };
 
-__device__ __forceinline__ bool kept_at(const int32_t* __restrict__ cell,
-                                        const uint8_t* __restrict__ land, int64_t i, int64_t n) {
-  return i < n && !land[cell[i]];
-}
-
-__global__ __launch_bounds__(kCompBlock) void k_land_tile_counts(const int32_t* __restrict__ cell,
+template <class CT>
+__global__ __launch_bounds__(kCompBlock) void k_land_tile_counts(const CT* __restrict__ cell,
                                                                 int64_t n,
                                                                 const uint8_t* __restrict__ land,
                                                                 int32_t* __restrict__ tile_cnt) {
-  const int64_t i0 = (int64_t)blockIdx.x * kCompTile + threadIdx.x;
   int32_t cl[kCompItems];
+  if constexpr (sizeof(CT) == 2) {
+    // 16-bit cells: a thread takes 16 consecutive cells as two 16-B loads (the count does not
+    // depend on which thread sees which point; 2-B loads, 128 B per wave instruction, were
+    // slower than the int32 form's: 68 against 50 us at 1000 frames)
+    static_assert(kCompItems == 16, "two uint4 loads of eight 16-bit cells each");
+    const int64_t b = (int64_t)blockIdx.x * kCompTile + (int64_t)threadIdx.x * kCompItems;
+    if (b + kCompItems <= n) {
+      const uint4* p = reinterpret_cast<const uint4*>(cell + b);  // (tiles start 8 KiB apart)
+      const uint4 lo = p[0], hi = p[1];
+      const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
 #pragma unroll
-  for (int k = 0; k < kCompItems; ++k) {
-    const int64_t i = i0 + (int64_t)k * kCompBlock;
-    cl[k] = (i < n) ? cell[i] : -1;
+      for (int q = 0; q < 8; ++q) {
+        cl[2 * q] = (int32_t)(w[q] & 0xffffu);
+        cl[2 * q + 1] = (int32_t)(w[q] >> 16);
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < kCompItems; ++k) cl[k] = (b + k < n) ? (int32_t)cell[b + k] : -1;
+    }
+  } else {
+    const int64_t i0 = (int64_t)blockIdx.x * kCompTile + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < kCompItems; ++k) {
+      const int64_t i = i0 + (int64_t)k * kCompBlock;
+      cl[k] = (i < n) ? cell[i] : -1;
+    }
   }
   uint32_t lnd[kCompItems];  // branch-free: the flags' loads in flight together (>= 1 cell)
 #pragma unroll
@@ -414,13 +439,20 @@ __global__ __launch_bounds__(kCompBlock) void k_land_tile_counts(const int32_t* 
   }
 }
 
+// OFFS (the stack driver's narrow path): no per-point frame slots in or out (pf, pfo unused);
+// a point's frame comes from the frame offsets fo[0 .. F] of the input (frame_index.h): one
+// search for the frame of the tile's first point, then one wave-uniform step per offset that
+// falls inside the tile (usually none or one; any number, runs of empty frames included).
+// CT, VT: the cells' and the intensities' element types (see the grid kernels; v is only copied).
+template <bool OFFS, class CT, class VT>
 __global__ __launch_bounds__(kCompBlock) void k_land_compact(
-    const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ v,
+    const float* __restrict__ x, const float* __restrict__ y, const VT* __restrict__ v,
     const int32_t* __restrict__ g, const int32_t* __restrict__ pf, int64_t n,
-    const int32_t* __restrict__ cell, const uint8_t* __restrict__ land,
+    const CT* __restrict__ cell, const uint8_t* __restrict__ land,
     const int32_t* __restrict__ tile_base, float* __restrict__ xo, float* __restrict__ yo,
-    float* __restrict__ vo, int32_t* __restrict__ go, int32_t* __restrict__ pfo,
-    float* __restrict__ to, BoundsPart* __restrict__ part, int64_t t_base) {
+    VT* __restrict__ vo, int32_t* __restrict__ go, int32_t* __restrict__ pfo,
+    float* __restrict__ to, BoundsPart* __restrict__ part, int64_t t_base,
+    const int64_t* __restrict__ fo, int F) {
   constexpr int NW = kCompBlock / 64;
   const int lane = threadIdx.x & 63, w = threadIdx.x / 64;
   const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
@@ -461,20 +493,41 @@ __global__ __launch_bounds__(kCompBlock) void k_land_compact(
   const int64_t tb = tile_base[blockIdx.x];
   uint32_t mnx = 0xffffffffu, mxx = 0u, mny = 0xffffffffu, mxy = 0u;
   int mnf = INT_MAX, mxf = INT_MIN, flags = 0;
+  const int64_t tile_lo = (int64_t)blockIdx.x * kCompTile;  // < n: the grid is ceil(n / tile)
+  const int64_t tile_hi = min(tile_lo + kCompTile, n);
+  int f0 = 0;  // (block-uniform) frame of the tile's first point
+  if constexpr (OFFS) f0 = __builtin_amdgcn_readfirstlane(frame_of_point(fo, F, tile_lo));
   constexpr int kB = 4;  // items per batch of loads
 #pragma unroll
   for (int k0 = 0; k0 < kCompItems; k0 += kB) {
     int fb[kB], fp[kB], gb[kB];
-    float xb[kB], yb[kB], vb[kB];
+    float xb[kB], yb[kB];
+    VT vb[kB];
 #pragma unroll
     for (int u = 0; u < kB; ++u) {
       const int64_t i = min(i0 + (int64_t)(k0 + u) * kCompBlock, n - 1);
-      fb[u] = pf[i];
-      fp[u] = pf[i > 0 ? i - 1 : 0];
+      if constexpr (OFFS) {
+        fb[u] = f0;
+        fp[u] = 0;
+      } else {
+        fb[u] = pf[i];
+        fp[u] = pf[i > 0 ? i - 1 : 0];
+      }
       xb[u] = x[i];
       yb[u] = y[i];
       vb[u] = v[i];
       gb[u] = go ? g[i] : 0;
+    }
+    if constexpr (OFFS) {
+      // frame = f0 + the offsets after fo[f0] that are <= i; those inside the tile are the only
+      // ones that can be (fo ascends: the loop ends at the first one at or past the tile's end)
+      for (int q = f0 + 1; q < F; ++q) {
+        const int64_t o = fo[q];  // (uniform)
+        if (o >= tile_hi) break;
+#pragma unroll
+        for (int u = 0; u < kB; ++u)
+          fb[u] += (i0 + (int64_t)(k0 + u) * kCompBlock >= o) ? 1 : 0;
+      }
     }
 #pragma unroll
     for (int u = 0; u < kB; ++u) {
@@ -484,8 +537,9 @@ __global__ __launch_bounds__(kCompBlock) void k_land_compact(
     const uint64_t bk = __ballot(kp);
     if (i < n) {
       const int f = fb[u];
-      // input order; the kept points descend only if the input does
-      if (i > 0 && f < fp[u]) flags |= 2;
+      // input order; the kept points descend only if the input does (OFFS: frames from
+      // ascending offsets cannot descend by construction, the flag stays clear)
+      if (!OFFS && i > 0 && f < fp[u]) flags |= 2;
       if (kp) {
         const int64_t o = tb + cw[k * NW + w] + __popcll(bk & lt);
         const float px = xb[u], py = yb[u];
@@ -493,7 +547,7 @@ __global__ __launch_bounds__(kCompBlock) void k_land_compact(
         yo[o] = py;
         vo[o] = vb[u];
         if (go) go[o] = gb[u];
-        pfo[o] = f;
+        if constexpr (!OFFS) pfo[o] = f;
         to[o] = (float)(t_base + (int64_t)f);  // (t_base: the shard driver's first frame)
         if (!isfinite(px) || !isfinite(py)) flags |= 1;
         const uint32_t a = f2ord(px), b = f2ord(py);
@@ -561,6 +615,48 @@ __global__ void k_land_new_off(const int32_t* __restrict__ n_kept_dev,
     }
   }
   if (lane == 0) new_off[f] = (f == n_frames) ? nk : lo;
+}
+
+// The same new_off without the kept points' frame slots: k_land_compact writes a tile's kept
+// points in index order, so new_off[f] = tile_base[T] + (kept points of tile T below index
+// fo[f]), T = fo[f] / kCompTile (new_off_split, frame_index.h); tile_base[tile count] is the kept
+// count.  One block per frame over at most one tile of cells, a thread's cells and then their
+// land flags loaded together like k_land_tile_counts' (one wave per frame walking the cells 64
+// at a time, two dependent loads per step, took 37 us at 1000 frames against the searched
+// form's 8).
+template <class CT>
+__global__ __launch_bounds__(kCompBlock) void k_land_new_off_tiles(
+    const int32_t* __restrict__ tile_base, const CT* __restrict__ cell,
+    const uint8_t* __restrict__ land, const int64_t* __restrict__ fo,
+    int64_t* __restrict__ new_off) {
+  const int f = blockIdx.x;  // 0 .. n_frames
+  int64_t T;
+  int32_t r;
+  new_off_split(fo[f], kCompTile, &T, &r);
+  const int64_t b = T * kCompTile;  // b + r = fo[f] <= n: every index below b + r is a point
+  int32_t cl[kCompItems];
+#pragma unroll
+  for (int k = 0; k < kCompItems; ++k) {
+    const int j = k * kCompBlock + (int)threadIdx.x;
+    cl[k] = (j < r) ? (int32_t)cell[b + j] : -1;
+  }
+  uint32_t lnd[kCompItems];
+#pragma unroll
+  for (int k = 0; k < kCompItems; ++k) lnd[k] = land[cl[k] >= 0 ? cl[k] : 0];
+  int c = 0;
+#pragma unroll
+  for (int k = 0; k < kCompItems; ++k) c += (cl[k] >= 0 && !lnd[k]) ? 1 : 0;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+  __shared__ int ws[kCompBlock / 64];
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x / 64] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int t = 0;
+#pragma unroll
+    for (int w = 0; w < kCompBlock / 64; ++w) t += ws[w];
+    new_off[f] = (int64_t)tile_base[T] + t;
+  }
 }
 
 // the tiles' partials -> Bounds (what k_bounds<2> gives for the kept points with t = frame
@@ -679,16 +775,21 @@ __global__ void k_zero_land(int32_t* __restrict__ cnt, double* __restrict__ tot,
 // cell_out (nullable, [n], int32 cells < 2^31): each point's grid cell, for land_filter_cells
 // u8_vals: every val is an integer in [0, 255] (points of a u8 echo; packed-atomic kernel)
 // zero_also (nullable): a 64-bit device counter zeroed with the grid
-int32_t land_grid_cells(const float* x, const float* y, const float* val, int64_t n,
-                        const double* xe, int32_t nxe, const double* ye, int32_t nye,
-                        int32_t* cnt, double* tot, int32_t* cell_out, hipStream_t st,
-                        int32_t u8_vals, int64_t* zero_also) {
+template <class CT, class VT>
+static int32_t land_grid_cells_t(const float* x, const float* y, const VT* val, int64_t n,
+                                 const double* xe, int32_t nxe, const double* ye, int32_t nye,
+                                 int32_t* cnt, double* tot, CT* cell_out, hipStream_t st,
+                                 int32_t u8_vals, int64_t* zero_also) {
   if (nxe < 2 || nye < 2) {
     set_error("rpt_land_grid: need at least two edges per axis");
     return RPT_EINVAL;
   }
   const int64_t cells = (int64_t)(nxe - 1) * (nye - 1);
-  if (cell_out && cells >= (int64_t(1) << 31)) cell_out = nullptr;
+  if (sizeof(CT) == 4 && cell_out && cells >= (int64_t(1) << 31)) cell_out = nullptr;
+  if (sizeof(CT) == 2 && cell_out && cells > 65536) {
+    set_error("land_grid_cells: more than 65,536 cells do not fit 16-bit cell ids");
+    return RPT_EINVAL;
+  }
   hipLaunchKernelGGL(k_zero_land, dim3(grid_for(cells, 256, 1024)), dim3(256), 0, st, cnt, tot,
                      cells, zero_also);
   RPT_CHECK_LAUNCH();
@@ -702,28 +803,51 @@ int32_t land_grid_cells(const float* x, const float* y, const float* val, int64_
   const int gb = grid_for(n, kGridBlock, std::max(n_cu, 1));
   if (u8_vals && lds_u8 <= 150 * 1024 && (n + gb - 1) / gb < (int64_t(1) << 24) &&
       ab().land_u8) {
-    RPT_HIP(hipFuncSetAttribute((const void*)k_land_grid_lds_u8,
+    RPT_HIP(hipFuncSetAttribute((const void*)k_land_grid_lds_u8<CT, VT>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_u8));
-    hipLaunchKernelGGL(k_land_grid_lds_u8, dim3(gb), dim3(kGridBlock), lds_u8, st, x, y, val, n,
+    hipLaunchKernelGGL((k_land_grid_lds_u8<CT, VT>), dim3(gb), dim3(kGridBlock), lds_u8, st, x, y, val, n,
                        xe, nxe, ye, nye, cnt, tot, cell_out);
   } else if (cells <= kLdsGridCells && lds <= 150 * 1024) {
-    RPT_HIP(hipFuncSetAttribute((const void*)k_land_grid_lds,
+    RPT_HIP(hipFuncSetAttribute((const void*)k_land_grid_lds<CT, VT>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_land_grid_lds, dim3(gb),
+    hipLaunchKernelGGL((k_land_grid_lds<CT, VT>), dim3(gb),
                        dim3(kGridBlock), lds, st, x, y, val, n, xe, nxe, ye, nye, cnt, tot,
                        cell_out);
   } else {
-    hipLaunchKernelGGL(k_land_grid, dim3(grid_for(n, kBlock, 4096)), dim3(kBlock), 0, st, x, y,
-                       val, n, xe, nxe, ye, nye, cnt, tot, cell_out);
+    hipLaunchKernelGGL((k_land_grid<CT, VT>), dim3(grid_for(n, kBlock, 4096)), dim3(kBlock), 0, st, x,
+                       y, val, n, xe, nxe, ye, nye, cnt, tot, cell_out);
   }
   RPT_CHECK_LAUNCH();
   return RPT_OK;
 }
 
+// cell16_out (nullable; grids of at most 65,536 cells): the per-point cells as uint16_t instead
+// of cell_out; val8 (nullable): the values as uint8_t samples instead of val (u8_vals holds by
+// construction) -- both the stack driver's narrow path
+int32_t land_grid_cells(const float* x, const float* y, const float* val, int64_t n,
+                        const double* xe, int32_t nxe, const double* ye, int32_t nye,
+                        int32_t* cnt, double* tot, int32_t* cell_out, hipStream_t st,
+                        int32_t u8_vals, int64_t* zero_also, uint16_t* cell16_out,
+                        const uint8_t* val8) {
+  if (val8 && cell16_out)
+    return land_grid_cells_t<uint16_t, uint8_t>(x, y, val8, n, xe, nxe, ye, nye, cnt, tot,
+                                                cell16_out, st, 1, zero_also);
+  if (val8)
+    return land_grid_cells_t<int32_t, uint8_t>(x, y, val8, n, xe, nxe, ye, nye, cnt, tot,
+                                               cell_out, st, 1, zero_also);
+  if (cell16_out) {
+    set_error("land_grid_cells: 16-bit cells come with u8 values");
+    return RPT_EINVAL;
+  }
+  return land_grid_cells_t<int32_t, float>(x, y, val, n, xe, nxe, ye, nye, cnt, tot, cell_out,
+                                           st, u8_vals, zero_also);
+}
+
 int32_t land_grid(const float* x, const float* y, const float* val, int64_t n, const double* xe,
                   int32_t nxe, const double* ye, int32_t nye, int32_t* cnt, double* tot,
                   hipStream_t st) {
-  return land_grid_cells(x, y, val, n, xe, nxe, ye, nye, cnt, tot, nullptr, st, 0, nullptr);
+  return land_grid_cells(x, y, val, n, xe, nxe, ye, nye, cnt, tot, nullptr, st, 0, nullptr,
+                         nullptr, nullptr);
 }
 
 // n_land_dev: int32 land-cell counter on the device, zeroed by the caller (no readback)
@@ -811,11 +935,20 @@ int32_t land_filter_cells(const float* x, const float* y, const float* v, const 
 // their times to (float32 frame slot), new_off[n_frames + 1] (device: first kept point per
 // frame slot, kept count last) and the kept points' ST-DBSCAN bounds (*bounds_out, device).
 // pf must be non-decreasing (the stack's frame-major order).  No synchronisation.
+// frame_off (nullable; device, [n_frames + 1], frame_off[n_frames] = n): the input's frame
+// offsets instead of pf; then pf and pfo are not touched (the stack driver's narrow path).
+// cell16 (nullable, with frame_off only): the cells as uint16_t instead of cell.
+// v8, vo8 (with frame_off, and only then): the intensities as uint8_t samples instead of v, vo.
 int32_t land_compact_dev(const float* x, const float* y, const float* v, const int32_t* g,
                          const int32_t* pf, int64_t n, const int32_t* cell, const uint8_t* land,
                          int32_t n_frames, float* xo, float* yo, float* vo, int32_t* go,
                          int32_t* pfo, float* to, int64_t* new_off, Bounds* bounds_out,
-                         hipStream_t st, int64_t t_base) {
+                         hipStream_t st, int64_t t_base, const int64_t* frame_off,
+                         const uint16_t* cell16, const uint8_t* v8, uint8_t* vo8) {
+  if ((frame_off != nullptr) != (v8 && vo8) || (cell16 && !frame_off)) {
+    set_error("land_compact_dev: frame offsets, u8 intensities and 16-bit cells come together");
+    return RPT_EINVAL;
+  }
   if (n < 0 || n >= (int64_t(1) << 31) - 1 || n_frames < 0) {
     set_error("land_compact_dev: bad sizes");
     return RPT_EINVAL;
@@ -830,14 +963,33 @@ int32_t land_compact_dev(const float* x, const float* y, const float* v, const i
   int32_t* cnt = sc.carve_n<int32_t>(nt + 1);
   int32_t* base = sc.carve_n<int32_t>(nt + 1);
   BoundsPart* part = sc.carve_n<BoundsPart>(nt);
-  hipLaunchKernelGGL(k_land_tile_counts, dim3((unsigned)nt), dim3(kCompBlock), 0, st, cell, n,
-                     land, cnt);
+  if (cell16)
+    hipLaunchKernelGGL(k_land_tile_counts<uint16_t>, dim3((unsigned)nt), dim3(kCompBlock), 0, st,
+                       cell16, n, land, cnt);
+  else
+    hipLaunchKernelGGL(k_land_tile_counts<int32_t>, dim3((unsigned)nt), dim3(kCompBlock), 0, st,
+                       cell, n, land, cnt);
   RPT_CHECK_LAUNCH();
   RPT_TRY(exclusive_scan_total_i32(cnt, base, nt, st));
-  hipLaunchKernelGGL(k_land_compact, dim3((unsigned)nt), dim3(kCompBlock), 0, st, x, y, v, g, pf,
-                     n, cell, land, base, xo, yo, vo, go, pfo, to, part, t_base);
-  hipLaunchKernelGGL(k_land_new_off, dim3((n_frames + 1 + 3) / 4), dim3(256), 0, st, base + nt,
-                     pfo, n_frames, new_off);
+  if (frame_off && n > 0 && cell16) {
+    hipLaunchKernelGGL((k_land_compact<true, uint16_t, uint8_t>), dim3((unsigned)nt),
+                       dim3(kCompBlock), 0, st, x, y, v8, g, nullptr, n, cell16, land, base, xo,
+                       yo, vo8, go, nullptr, to, part, t_base, frame_off, n_frames);
+    hipLaunchKernelGGL(k_land_new_off_tiles<uint16_t>, dim3(n_frames + 1), dim3(kCompBlock), 0,
+                       st, base, cell16, land, frame_off, new_off);
+  } else if (frame_off && n > 0) {
+    hipLaunchKernelGGL((k_land_compact<true, int32_t, uint8_t>), dim3((unsigned)nt),
+                       dim3(kCompBlock), 0, st, x, y, v8, g, nullptr, n, cell, land, base, xo, yo,
+                       vo8, go, nullptr, to, part, t_base, frame_off, n_frames);
+    hipLaunchKernelGGL(k_land_new_off_tiles<int32_t>, dim3(n_frames + 1), dim3(kCompBlock), 0,
+                       st, base, cell, land, frame_off, new_off);
+  } else {
+    hipLaunchKernelGGL((k_land_compact<false, int32_t, float>), dim3((unsigned)nt), dim3(kCompBlock), 0, st, x, y,
+                       v, g, pf, n, cell, land, base, xo, yo, vo, go, pfo, to, part, t_base,
+                       nullptr, 0);
+    hipLaunchKernelGGL(k_land_new_off, dim3((n_frames + 1 + 3) / 4), dim3(256), 0, st, base + nt,
+                       pfo, n_frames, new_off);
+  }
   hipLaunchKernelGGL(k_land_compact_final, dim3(1), dim3(kFinBlock), 0, st, part, (int)nt,
                      base + nt, bounds_out, t_base);
   RPT_CHECK_LAUNCH();

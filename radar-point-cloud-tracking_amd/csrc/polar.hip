@@ -529,13 +529,15 @@ __global__ void k_file_counts_groups(const int64_t* __restrict__ gprefix, int64_
 // earlier run) is repeated by the caller when the count says it did not fit.
 // LIST: the groups are the first *list_n entries of list (the unstaged groups of the expand
 // write below), not 0 .. n_groups-1.
-template <bool HI, bool STAGED, bool LIST = false>
+// VT: the element type of val, float or -- the stack driver's narrow path -- uint8_t (the
+// sample itself, the entry's low byte).
+template <bool HI, bool STAGED, bool LIST = false, class VT = float>
 __global__ __launch_bounds__(kBlock, 8) void k_group_write_u8(
     const uint8_t* __restrict__ echo, uint32_t n_groups, GroupMap gm, uint32_t K, int stride,
     const float* __restrict__ scale, const float* __restrict__ cos_t,
     const float* __restrict__ sin_t, const int32_t* __restrict__ gain,
     const int64_t* __restrict__ gprefix, const int64_t* __restrict__ file_offsets,
-    int files_per_frame, float* __restrict__ x, float* __restrict__ y, float* __restrict__ val,
+    int files_per_frame, float* __restrict__ x, float* __restrict__ y, VT* __restrict__ val,
     int32_t* __restrict__ gain_out, int32_t* __restrict__ pf_out, int64_t cap,
     const uint32_t* __restrict__ entries, const uint32_t* __restrict__ list = nullptr,
     const uint32_t* __restrict__ list_n = nullptr, uint32_t* __restrict__ bpart = nullptr) {
@@ -621,7 +623,7 @@ __global__ __launch_bounds__(kBlock, 8) void k_group_write_u8(
       x[oo] = px;
       y[oo] = py;
       if (bpart) xb.add(px, py);
-      val[oo] = (float)(ent & 0xffu);
+      val[oo] = (VT)(ent & 0xffu);
       if (gain_out) gain_out[oo] = g;
       if (pf_out) pf_out[oo] = fr;
     }
@@ -742,13 +744,14 @@ __device__ __forceinline__ uint32_t lds_find(const uint64_t* s_win, uint32_t wn,
 }
 
 // VEC: every output array is 16-B aligned (float4 / int4 stores of a thread's 4 outputs)
-template <bool VEC>
+// VT: as k_group_write_u8's (uint8_t: a thread's four intensities are one 4-byte store)
+template <bool VEC, class VT = float>
 __global__ __launch_bounds__(kBlock) void k_expand_write(
     const uint64_t* __restrict__ gword, uint32_t n_groups, GroupMap gm, uint32_t stride,
     const float* __restrict__ scale, const float* __restrict__ cos_t,
     const float* __restrict__ sin_t, const int32_t* __restrict__ gain,
     const int64_t* __restrict__ total_out, int files_per_frame, float* __restrict__ x,
-    float* __restrict__ y, float* __restrict__ val, int32_t* __restrict__ gain_out,
+    float* __restrict__ y, VT* __restrict__ val, int32_t* __restrict__ gain_out,
     int32_t* __restrict__ pf_out, int64_t cap, const uint32_t* __restrict__ entries,
     uint32_t* __restrict__ bpart = nullptr) {
   // bpart (nullable): this block's xy-bounds partial of the outputs it writes (XyBounds)
@@ -900,7 +903,12 @@ __global__ __launch_bounds__(kBlock) void k_expand_write(
         const uint64_t o = Ob + h;
         *reinterpret_cast<float4*>(x + o) = make_float4(ox[h], ox[h + 1], ox[h + 2], ox[h + 3]);
         *reinterpret_cast<float4*>(y + o) = make_float4(oy[h], oy[h + 1], oy[h + 2], oy[h + 3]);
-        *reinterpret_cast<float4*>(val + o) = make_float4(ov[h], ov[h + 1], ov[h + 2], ov[h + 3]);
+        if constexpr (sizeof(VT) == 1)
+          *reinterpret_cast<uint32_t*>(val + o) =
+              (ent[h] & 0xffu) | ((ent[h + 1] & 0xffu) << 8) | ((ent[h + 2] & 0xffu) << 16) |
+              ((ent[h + 3] & 0xffu) << 24);
+        else
+          *reinterpret_cast<float4*>(val + o) = make_float4(ov[h], ov[h + 1], ov[h + 2], ov[h + 3]);
         if (gain_out)
           *reinterpret_cast<int4*>(gain_out + o) = make_int4(og[h], og[h + 1], og[h + 2], og[h + 3]);
         if (pf_out)
@@ -913,7 +921,7 @@ __global__ __launch_bounds__(kBlock) void k_expand_write(
         const uint64_t oo = Ob + k;
         x[oo] = ox[k];
         y[oo] = oy[k];
-        val[oo] = ov[k];
+        val[oo] = (VT)(ent[k] & 0xffu);
         if (gain_out) gain_out[oo] = og[k];
         if (pf_out) pf_out[oo] = op[k];
       }
@@ -1016,10 +1024,10 @@ int32_t count_impl(const T* echo, int64_t n_files, int rows, int bins, float thr
   return RPT_OK;
 }
 
-template <class T>
+template <class T, class VT = float>
 int32_t write_impl(const T* echo, int64_t n_files, int rows, int bins, float thr, int stride,
                    RowGeo geo, const int32_t* gain, const int64_t* row_prefix,
-                   const int64_t* file_offsets, int fpf, float* x, float* y, float* v,
+                   const int64_t* file_offsets, int fpf, float* x, float* y, VT* v,
                    int32_t* gout, int32_t* pf, hipStream_t st, int64_t cap = INT64_MAX,
                    const uint32_t* entries = nullptr, uint32_t* bnd = nullptr,
                    bool* bnd_done = nullptr) {
@@ -1059,19 +1067,19 @@ int32_t write_impl(const T* echo, int64_t n_files, int rows, int bins, float thr
       auto al16 = [](const void* q) { return ((uintptr_t)q & 15u) == 0; };
       const bool vec4 = al16(x) && al16(y) && al16(v) && (!gout || al16(gout)) && (!pf || al16(pf));
       if (vec4)
-        hipLaunchKernelGGL(k_expand_write<true>, dim3(kExpandBlocks), dim3(kBlock), 0, st, gword,
+        hipLaunchKernelGGL((k_expand_write<true, VT>), dim3(kExpandBlocks), dim3(kBlock), 0, st, gword,
                            (uint32_t)n_groups, gm, (uint32_t)stride, geo.scale, geo.cos_t,
                            geo.sin_t, gain, file_offsets + n_files, fpf, x, y, v, gout, pf, cap,
                            entries, bnd ? bnd + 4 : nullptr);
       else
-        hipLaunchKernelGGL(k_expand_write<false>, dim3(kExpandBlocks), dim3(kBlock), 0, st,
+        hipLaunchKernelGGL((k_expand_write<false, VT>), dim3(kExpandBlocks), dim3(kBlock), 0, st,
                            gword, (uint32_t)n_groups, gm, (uint32_t)stride, geo.scale, geo.cos_t,
                            geo.sin_t, gain, file_offsets + n_files, fpf, x, y, v, gout, pf, cap,
                            entries, bnd ? bnd + 4 : nullptr);
       RPT_CHECK_LAUNCH();
       const int lgrid = std::min(grid, kListBlocks);
 #define RPT_K1L(HI)                                                                            \
-  hipLaunchKernelGGL((k_group_write_u8<HI, false, true>), dim3(lgrid), dim3(kBlock), 0, st, e8, \
+  hipLaunchKernelGGL((k_group_write_u8<HI, false, true, VT>), dim3(lgrid), dim3(kBlock), 0, st, e8, \
                      (uint32_t)n_groups, gm, u8_k(T8), stride, geo.scale, geo.cos_t, geo.sin_t,  \
                      gain, row_prefix, file_offsets, fpf, x, y, v, gout, pf, cap, entries, list, \
                      list_n, bnd ? bnd + 4 + 4 * kExpandBlocks : nullptr)
@@ -1089,7 +1097,7 @@ int32_t write_impl(const T* echo, int64_t n_files, int rows, int bins, float thr
       return RPT_OK;
     }
 #define RPT_K1W(HI, M)                                                                       \
-  hipLaunchKernelGGL((k_group_write_u8<HI, M>), dim3(grid), dim3(kBlock), 0, st, e8,          \
+  hipLaunchKernelGGL((k_group_write_u8<HI, M, false, VT>), dim3(grid), dim3(kBlock), 0, st, e8,          \
                      (uint32_t)n_groups, gm, u8_k(T8), stride, geo.scale, geo.cos_t, geo.sin_t, \
                      gain, row_prefix, file_offsets, fpf, x, y, v, gout, pf, cap, entries)
     if (entries) {
@@ -1108,6 +1116,9 @@ int32_t write_impl(const T* echo, int64_t n_files, int rows, int bins, float thr
     return RPT_ENOTSUP;
   } else if (grouped_u8(echo, bins)) {
     set_error("rpt_polar_write: u8 sweeps take per-row scale geometry");
+    return RPT_ENOTSUP;
+  } else if constexpr (sizeof(VT) == 1) {
+    set_error("rpt_polar_write: u8 intensities need u8 sweeps of 1024 bins");
     return RPT_ENOTSUP;
   } else if (vec) {
     const int grid = grid_for(n_rows, kWavesPerBlock, 16384);
@@ -1133,6 +1144,24 @@ __global__ void k_frame_times(const int32_t* __restrict__ pf, int64_t n,
     const int32_t f = pf[i];
     t[i] = (float)(ids ? ids[f] : (int64_t)f);
   }
+}
+
+// frame slots from frame offsets: block f fills the points [off[f], off[f + 1]) of frame f
+__global__ void k_frame_fill(const int64_t* __restrict__ off, float* __restrict__ t,
+                             int32_t* __restrict__ pf) {
+  const int32_t f = blockIdx.x;
+  const int64_t hi = off[f + 1];
+  for (int64_t i = off[f] + threadIdx.x; i < hi; i += blockDim.x) {
+    if (t) t[i] = (float)f;
+    if (pf) pf[i] = f;
+  }
+}
+
+__global__ void k_bytes_to_float(const uint8_t* __restrict__ in, int64_t n,
+                                 float* __restrict__ out) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x)
+    out[i] = (float)in[i];
 }
 
 __global__ void k_polar_dense(const float* __restrict__ cos_t, const float* __restrict__ sin_t,
@@ -1340,6 +1369,43 @@ int32_t polar_write_cap(const uint8_t* echo, int64_t n_files, int32_t rows, floa
                              bnd_done);
 }
 
+// The same two with uint8_t intensities (the samples themselves): u8 sweeps of 1024 bins with
+// 16-B aligned rows only (the stack driver's narrow path).
+int32_t polar_write(const uint8_t* echo, int64_t n_files, int32_t rows, const float* scale,
+                    const float* cos_t, const float* sin_t, const int32_t* gain, float thr,
+                    int32_t stride, const int64_t* row_prefix, const int64_t* file_offsets,
+                    int32_t fpf, float* x, float* y, uint8_t* v, int32_t* gout, int32_t* pf,
+                    hipStream_t st, const uint32_t* entries, uint32_t* bnd, bool* bnd_done) {
+  if (bnd_done) *bnd_done = false;
+  if (n_files == 0) return RPT_OK;
+  if (!grouped_u8(echo, 1024) || fpf < 1 || !scale || !cos_t || !sin_t || !row_prefix ||
+      !file_offsets || !x || !y || !v || stride < 1) {
+    set_error("rpt_polar_write: bad arguments");
+    return RPT_EINVAL;
+  }
+  RowGeo geo{scale, nullptr, cos_t, sin_t};
+  return write_impl<uint8_t, uint8_t>(echo, n_files, rows, 1024, thr, stride, geo, gain,
+                                      row_prefix, file_offsets, fpf, x, y, v, gout, pf, st,
+                                      INT64_MAX, entries, bnd, bnd_done);
+}
+
+int32_t polar_write_cap(const uint8_t* echo, int64_t n_files, int32_t rows, float thr,
+                        int32_t stride, const float* scale, const float* cos_t,
+                        const float* sin_t, const int32_t* gain, const int64_t* row_prefix,
+                        const int64_t* file_offsets, int32_t fpf, float* x, float* y, uint8_t* v,
+                        int32_t* gout, int32_t* pf, int64_t cap, hipStream_t st,
+                        const uint32_t* entries, uint32_t* bnd, bool* bnd_done) {
+  if (bnd_done) *bnd_done = false;
+  if (!grouped_u8(echo, 1024)) {
+    set_error("polar_write_cap: u8 sweeps of 1024 bins with 16-B aligned rows only");
+    return RPT_ENOTSUP;
+  }
+  RowGeo geo{scale, nullptr, cos_t, sin_t};
+  return write_impl<uint8_t, uint8_t>(echo, n_files, rows, 1024, thr, stride, geo, gain,
+                                      row_prefix, file_offsets, fpf, x, y, v, gout, pf, st, cap,
+                                      entries, bnd, bnd_done);
+}
+
 // words of the bnd buffer of polar_write / polar_write_cap: 4 + the blocks' partials
 int64_t polar_bounds_words() { return 4 + 4 * (int64_t)(kExpandBlocks + kListBlocks); }
 
@@ -1380,6 +1446,20 @@ int32_t frame_times(const int32_t* pf, int64_t n, const int64_t* ids, float* t, 
   if (n == 0) return RPT_OK;
   hipLaunchKernelGGL(k_frame_times, dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, pf, n, ids, t,
                      (const int64_t*)nullptr);
+  RPT_CHECK_LAUNCH();
+  return RPT_OK;
+}
+
+int32_t frame_fill(const int64_t* off, int32_t n_frames, float* t, int32_t* pf, hipStream_t st) {
+  if (n_frames <= 0 || (!t && !pf)) return RPT_OK;
+  hipLaunchKernelGGL(k_frame_fill, dim3((unsigned)n_frames), dim3(256), 0, st, off, t, pf);
+  RPT_CHECK_LAUNCH();
+  return RPT_OK;
+}
+
+int32_t bytes_to_float(const uint8_t* in, int64_t n, float* out, hipStream_t st) {
+  if (n <= 0) return RPT_OK;
+  hipLaunchKernelGGL(k_bytes_to_float, dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, in, n, out);
   RPT_CHECK_LAUNCH();
   return RPT_OK;
 }

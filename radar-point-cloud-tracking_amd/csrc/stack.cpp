@@ -139,6 +139,11 @@ int32_t rpt_stack::run(const rpt_stack_params& p, const void* echo, const float*
   // so K1 reads the echo once (ab().k1_stage off: two full reads)
   const bool grouped = p.echo_dtype == RPT_ECHO_U8 && p.bins == 1024 &&
                        (uintptr_t)echo % 16 == 0;
+  // the narrow point layout, on the same condition: no per-point frame slots (pf, pf2 stay
+  // unallocated) -- the points are in frame order, so the land compaction, K9 and the hand-back
+  // take a point's frame from the frame offsets (frame_index.h) -- and the intensities as the u8
+  // samples themselves (v8, v8b instead of v, v2; float32 again on hand-back)
+  narrow = grouped;
   uint32_t* mk = nullptr;
   if (grouped && ab().k1_stage) {
     RPT_TRY(k1_stage.ensure((size_t)polar_stage_words(n_files, p.rows), st));
@@ -159,13 +164,13 @@ int32_t rpt_stack::run(const rpt_stack_params& p, const void* echo, const float*
   bool k1_bounds = false;
   if (grouped && mk) RPT_TRY(k1_bnd.ensure((size_t)polar_bounds_words(), st));
   uint32_t* kb = (grouped && mk) ? k1_bnd.p : nullptr;
-  if (grouped && x.p && y.p && v.p && g.p && pf.p) {
-    spec_cap = (int64_t)std::min({x.cap, y.cap, v.cap, g.cap, pf.cap});
+  if (grouped && x.p && y.p && v8.p && g.p) {
+    spec_cap = (int64_t)std::min({x.cap, y.cap, v8.cap, g.cap});
     if (!ev_rb) RPT_HIP(hipEventCreateWithFlags(&ev_rb, hipEventDisableTiming));
     RPT_HIP(hipEventRecord(ev_rb, st));
     RPT_TRY(polar_write_cap((const uint8_t*)echo, n_files, p.rows, p.threshold, p.stride, scale,
-                            cos_t, sin_t, gain, row_prefix.p, file_off.p, G, x.p, y.p, v.p,
-                            gain ? g.p : nullptr, pf.p, spec_cap, st, mk, kb, &k1_bounds));
+                            cos_t, sin_t, gain, row_prefix.p, file_off.p, G, x.p, y.p, v8.p,
+                            gain ? g.p : nullptr, nullptr, spec_cap, st, mk, kb, &k1_bounds));
     RPT_HIP(hipEventSynchronize(ev_rb));  // the readback only; the write keeps running
   } else {
     RPT_TRY(wait_stream(st));
@@ -181,12 +186,19 @@ int32_t rpt_stack::run(const rpt_stack_params& p, const void* echo, const float*
   if (N > spec_cap) {
     RPT_TRY(x.ensure(cap, st));
     RPT_TRY(y.ensure(cap, st));
-    RPT_TRY(v.ensure(cap, st));
     RPT_TRY(g.ensure(cap, st));
-    RPT_TRY(pf.ensure(cap, st));
-    RPT_TRY(polar_write(echo, p.echo_dtype, n_files, p.rows, p.bins, scale, cos_t, sin_t, gain,
-                        p.threshold, p.stride, row_prefix.p, file_off.p, G, x.p, y.p, v.p,
-                        gain ? g.p : nullptr, pf.p, st, mk, kb, &k1_bounds));
+    if (narrow) {
+      RPT_TRY(v8.ensure(cap, st));
+      RPT_TRY(polar_write((const uint8_t*)echo, n_files, p.rows, scale, cos_t, sin_t, gain,
+                          p.threshold, p.stride, row_prefix.p, file_off.p, G, x.p, y.p, v8.p,
+                          gain ? g.p : nullptr, nullptr, st, mk, kb, &k1_bounds));
+    } else {
+      RPT_TRY(v.ensure(cap, st));
+      RPT_TRY(pf.ensure(cap, st));
+      RPT_TRY(polar_write(echo, p.echo_dtype, n_files, p.rows, p.bins, scale, cos_t, sin_t, gain,
+                          p.threshold, p.stride, row_prefix.p, file_off.p, G, x.p, y.p, v.p,
+                          gain ? g.p : nullptr, pf.p, st, mk, kb, &k1_bounds));
+    }
   }
   RPT_TRY(k1turn.leave());
   if (timing) RPT_HIP(hipEventRecord(ev[1], st));
@@ -212,8 +224,9 @@ int32_t rpt_stack::run(const rpt_stack_params& p, const void* echo, const float*
   // ---- land filter (global grid over the stack, :954 gate: more than 10 built frames)
   float* cx = x.p;
   float* cy = y.p;
-  float* cv = v.p;
-  int32_t* cpf = pf.p;
+  float* cv = narrow ? nullptr : v.p;
+  uint8_t* cv8 = narrow ? v8.p : nullptr;
+  int32_t* cpf = narrow ? nullptr : pf.p;
   int64_t n_in_ = N;
   fo_in = fo_k1;
   r.n_land_cells = 0;
@@ -253,32 +266,45 @@ int32_t rpt_stack::run(const rpt_stack_params& p, const void* echo, const float*
     RPT_TRY(land_cnt.ensure((size_t)cells, st));
     RPT_TRY(land_tot.ensure((size_t)cells, st));
     RPT_TRY(land_mask.ensure((size_t)cells, st));
-    RPT_TRY(land_cell.ensure(cap, st));
+    // narrow path: 16-bit cell ids when the grid has at most 65,536 cells (with ab().land_u8
+    // off the filter keeps its float, int32-cell form)
+    const bool cell16 = narrow && cells <= 65536 && ab().land_u8;
+    if (cell16)
+      RPT_TRY(land_cell16.ensure(cap, st));
+    else
+      RPT_TRY(land_cell.ensure(cap, st));
     // the land-cell count accumulates (int32) into the low half of an int64 slot, zeroed with
     // the grid
     RPT_TRY(scal.ensure(4, st));
-    RPT_TRY(land_grid_cells(x.p, y.p, v.p, N, edges.p, nxe, edges.p + nxe, nye, land_cnt.p,
-                            land_tot.p, land_cell.p, st, p.echo_dtype == RPT_ECHO_U8 ? 1 : 0,
-                            reinterpret_cast<int64_t*>(scal.p)));
+    RPT_TRY(land_grid_cells(x.p, y.p, cv, N, edges.p, nxe, edges.p + nxe, nye, land_cnt.p,
+                            land_tot.p, cell16 ? nullptr : land_cell.p, st,
+                            p.echo_dtype == RPT_ECHO_U8 ? 1 : 0,
+                            reinterpret_cast<int64_t*>(scal.p), cell16 ? land_cell16.p : nullptr,
+                            cv8));
     RPT_TRY(land_mask_dev(land_cnt.p, land_tot.p, cells, n_built, p.land_persistence,
                           p.land_min_intensity, land_mask.p, reinterpret_cast<int32_t*>(scal.p),
                           st));
     RPT_TRY(x2.ensure(cap, st));
     RPT_TRY(y2.ensure(cap, st));
-    RPT_TRY(v2.ensure(cap, st));
+    if (narrow)
+      RPT_TRY(v8b.ensure(cap, st));
+    else
+      RPT_TRY(v2.ensure(cap, st));
     RPT_TRY(g2.ensure(cap, st));
-    RPT_TRY(pf2.ensure(cap, st));
+    if (!narrow) RPT_TRY(pf2.ensure(cap, st));
     RPT_TRY(new_off.ensure((size_t)F + 1, st));
     // one fused compaction: the kept points in order, their frame times and their ST-DBSCAN
     // bounds (the kept count new_off[F] stays on the device), read back with the offsets and the
     // land-cell count: ONE round trip
-    (void)fo_dev;
     RPT_TRY(t.ensure(cap, st));
     const size_t bnd_bytes = stdbscan_bounds_bytes();
     RPT_TRY(bnd.ensure(2 * bnd_bytes, st));
-    RPT_TRY(land_compact_dev(x.p, y.p, v.p, gain ? g.p : nullptr, pf.p, N, land_cell.p,
-                             land_mask.p, F, x2.p, y2.p, v2.p, gain ? g2.p : nullptr, pf2.p, t.p,
-                             new_off.p, reinterpret_cast<Bounds*>(bnd.p), st));
+    RPT_TRY(land_compact_dev(x.p, y.p, cv, gain ? g.p : nullptr, cpf, N, land_cell.p,
+                             land_mask.p, F, x2.p, y2.p, narrow ? nullptr : v2.p,
+                             gain ? g2.p : nullptr,
+                             narrow ? nullptr : pf2.p, t.p, new_off.p,
+                             reinterpret_cast<Bounds*>(bnd.p), st, 0, narrow ? fo_dev : nullptr,
+                             cell16 ? land_cell16.p : nullptr, cv8, narrow ? v8b.p : nullptr));
     int64_t* hn = reinterpret_cast<int64_t*>(down.p);
     PackList pl;
     pl.add(new_off.p, sizeof(int64_t) * (F + 1));
@@ -296,8 +322,9 @@ int32_t rpt_stack::run(const rpt_stack_params& p, const void* echo, const float*
                          reinterpret_cast<const char*>(hn + F + 2) + bnd_bytes);
     cx = x2.p;
     cy = y2.p;
-    cv = v2.p;
-    cpf = pf2.p;
+    cv = narrow ? nullptr : v2.p;
+    cv8 = narrow ? v8b.p : nullptr;
+    cpf = narrow ? nullptr : pf2.p;
     land_applied = true;
   }
   if (timing) RPT_HIP(hipEventRecord(ev[2], st));
@@ -313,8 +340,20 @@ int32_t rpt_stack::run(const rpt_stack_params& p, const void* echo, const float*
   RPT_TRY(labels.ensure(cap2, st));
   if (!land_applied) {  // with the land filter, the times and bounds came with its readback
     RPT_TRY(t.ensure(cap2, st));
-    RPT_TRY(frame_times(cpf, n_in_, nullptr, t.p, st));
+    if (narrow) {
+      // no land filter: the K1 offsets go up here (with it they rode behind the land edges)
+      RPT_TRY(fo_d.ensure((size_t)F + 1, st));
+      RPT_TRY(up.ensure(sizeof(int64_t) * ((size_t)F + 1), st));
+      std::memcpy(up.p, fo_k1.data(), sizeof(int64_t) * ((size_t)F + 1));
+      RPT_HIP(hipMemcpyAsync(fo_d.p, up.p, sizeof(int64_t) * ((size_t)F + 1),
+                             hipMemcpyHostToDevice, st));
+      RPT_TRY(frame_fill(fo_d.p, F, t.p, nullptr, st));
+    } else {
+      RPT_TRY(frame_times(cpf, n_in_, nullptr, t.p, st));
+    }
   }
+  // the frame offsets of the points that ST-DBSCAN and K9 see, on the device (narrow path)
+  const int64_t* fo_k9 = !narrow ? nullptr : land_applied ? new_off.p : fo_d.p;
   // ST-DBSCAN and K9 without readbacks in between: the cluster count and the segment count stay
   // on the device and come back with the results in ONE readback; the K9 sort runs with the
   // previous run's label bits and the summarize grid with its segment count, and both are
@@ -346,7 +385,8 @@ int32_t rpt_stack::run(const rpt_stack_params& p, const void* echo, const float*
   bool radix_used = false;
   RPT_TRY(cluster_summaries_dev(labels.p, cx, cy, cv, cpf, n_in_, F, bits, sc, seg_frame.p,
                                 seg_label.p, seg_count.p, seg_first.p, seg_cx.p, seg_cy.p,
-                                seg_mi.p, first_noise.p, &nseg_dev, k9_radix, &radix_used, st));
+                                seg_mi.p, first_noise.p, &nseg_dev, k9_radix, &radix_used, st,
+                                fo_k9, cv8));
   SegPack sp{seg_count.p, seg_first.p, first_noise.p, seg_frame.p,
              seg_label.p, seg_cx.p,    seg_cy.p,      seg_mi.p};
   size_t bytes = seg_pack_bytes(sc, F);
@@ -373,7 +413,8 @@ int32_t rpt_stack::run(const rpt_stack_params& p, const void* echo, const float*
       RPT_TRY(cluster_summaries_dev(labels.p, cx, cy, cv, cpf, n_in_, F, radix_bits_for(ncl),
                                     std::max<int64_t>(S, sc), seg_frame.p, seg_label.p,
                                     seg_count.p, seg_first.p, seg_cx.p, seg_cy.p, seg_mi.p,
-                                    first_noise.p, &nseg_dev, k9_radix, nullptr, st));
+                                    first_noise.p, &nseg_dev, k9_radix, nullptr, st, fo_k9,
+                                    cv8));
     sc_used = rerun ? sc : std::max<int64_t>(S, 1);
     for (int pass = 0; pass < 2; ++pass) {
       bytes = seg_pack_bytes(sc_used, F);
@@ -503,9 +544,18 @@ int32_t rpt_stack_points(const rpt_stack* h, float* x, float* y, float* intensit
   const bool l = h->land_applied;
   RPT_TRY(cp(x, l ? h->x2.p : h->x.p, 4));
   RPT_TRY(cp(y, l ? h->y2.p : h->y.p, 4));
-  RPT_TRY(cp(intensity, l ? h->v2.p : h->v.p, 4));
+  if (h->narrow) {  // kept as u8 samples: float32 again on hand-back
+    if (intensity) RPT_TRY(bytes_to_float(l ? h->v8b.p : h->v8.p, (int64_t)n, intensity, st));
+  } else {
+    RPT_TRY(cp(intensity, l ? h->v2.p : h->v.p, 4));
+  }
   RPT_TRY(cp(gain, l ? h->g2.p : h->g.p, 4));
-  RPT_TRY(cp(point_frame, l ? h->pf2.p : h->pf.p, 4));
+  if (h->narrow) {  // no frame slots were kept: filled from the offsets of the handed-back points
+    if (point_frame && n)
+      RPT_TRY(frame_fill(l ? h->new_off.p : h->fo_d.p, h->n_frames, nullptr, point_frame, st));
+  } else {
+    RPT_TRY(cp(point_frame, l ? h->pf2.p : h->pf.p, 4));
+  }
   RPT_TRY(cp(labels, h->labels.p, 4));
   return RPT_OK;
 }

@@ -37,7 +37,8 @@ int32_t bounds_xy(const float* x, const float* y, int64_t n, float* out4, hipStr
 int32_t land_grid_cells(const float* x, const float* y, const float* val, int64_t n,
                         const double* xe, int32_t nxe, const double* ye, int32_t nye,
                         int32_t* cnt, double* tot, int32_t* cell_out, hipStream_t st,
-                        int32_t u8_vals, int64_t* zero_also = nullptr);
+                        int32_t u8_vals, int64_t* zero_also = nullptr,
+                        uint16_t* cell16_out = nullptr, const uint8_t* val8 = nullptr);
 int32_t land_mask(const int32_t* cnt, const double* tot, int64_t cells, int64_t num_frames,
                   double pthr, double ithr, uint8_t* land, int64_t* n_land_host,
                   hipStream_t st);
@@ -48,7 +49,28 @@ int32_t land_compact_dev(const float* x, const float* y, const float* v, const i
                          const int32_t* pf, int64_t n, const int32_t* cell, const uint8_t* land,
                          int32_t n_frames, float* xo, float* yo, float* vo, int32_t* go,
                          int32_t* pfo, float* to, int64_t* new_off, Bounds* bounds_out,
-                         hipStream_t st, int64_t t_base = 0);
+                         hipStream_t st, int64_t t_base = 0,
+                         const int64_t* frame_off = nullptr, const uint16_t* cell16 = nullptr,
+                         const uint8_t* v8 = nullptr, uint8_t* vo8 = nullptr);
+// the u8-intensity forms (u8 sweeps of 1024 bins, 16-B aligned rows): v holds the samples
+int32_t polar_write_cap(const uint8_t* echo, int64_t n_files, int32_t rows, float thr,
+                        int32_t stride, const float* scale, const float* cos_t,
+                        const float* sin_t, const int32_t* gain, const int64_t* row_prefix,
+                        const int64_t* file_offsets, int32_t fpf, float* x, float* y, uint8_t* v,
+                        int32_t* gout, int32_t* pf, int64_t cap, hipStream_t st,
+                        const uint32_t* entries, uint32_t* bnd = nullptr,
+                        bool* bnd_done = nullptr);
+int32_t polar_write(const uint8_t* echo, int64_t n_files, int32_t rows, const float* scale,
+                    const float* cos_t, const float* sin_t, const int32_t* gain, float thr,
+                    int32_t stride, const int64_t* row_prefix, const int64_t* file_offsets,
+                    int32_t fpf, float* x, float* y, uint8_t* v, int32_t* gout, int32_t* pf,
+                    hipStream_t st, const uint32_t* entries, uint32_t* bnd = nullptr,
+                    bool* bnd_done = nullptr);
+// out[i] = (float)in[i]
+int32_t bytes_to_float(const uint8_t* in, int64_t n, float* out, hipStream_t st);
+// t[i] = (float)f and pf[i] = f (each nullable) for the points [off[f], off[f + 1]) of every
+// frame f: frame slots from device frame offsets off[0 .. n_frames]
+int32_t frame_fill(const int64_t* off, int32_t n_frames, float* t, int32_t* pf, hipStream_t st);
 int32_t stdbscan(const float* x, const float* y, const float* z, int64_t stride, const float* t,
                  int64_t n, double eps_space, double eps_time, int32_t min_samples,
                  int32_t* labels, rpt_stdbscan_stats* stats, hipStream_t st, int dim);
@@ -71,7 +93,8 @@ int32_t cluster_summaries_dev(const int32_t* labels, const float* x, const float
                               int64_t* o_count, int64_t* o_first, float* o_cx, float* o_cy,
                               float* o_mi, int64_t* frame_first_noise,
                               const int32_t** n_seg_dev, bool force_radix, bool* radix_used,
-                              hipStream_t st);
+                              hipStream_t st, const int64_t* frame_off = nullptr,
+                              const uint8_t* inten8 = nullptr);
 int32_t cluster_summaries(const int32_t* labels, const float* x, const float* y,
                           const float* inten, const int32_t* pf, int64_t n, int32_t n_frames,
                           int32_t n_clusters, int32_t* o_frame, int32_t* o_label,
@@ -200,6 +223,10 @@ struct rpt_stack {
   DevBuf<uint32_t> pack_d;  // packed readback staging
   rpt_k1_gate* k1_gate = nullptr;  // (not owned) rpt_stack_set_k1_gate
   DevBuf<int64_t> row_prefix, file_off, new_off, first_noise, seg_count, seg_first, scal;
+  DevBuf<int64_t> fo_d;  // narrow path without the land filter: the K1 frame offsets
+  DevBuf<uint16_t> land_cell16;  // narrow path: the land cells of a grid of <= 65,536 cells
+  DevBuf<uint8_t> v8, v8b;       // narrow path: the intensities (u8 samples), K1's and the kept
+  bool narrow = false;   // the last run kept no per-point frame slots (pf, pf2 unused)
   DevBuf<float> x, y, v, x2, y2, v2, t, seg_cx, seg_cy, seg_mi;
   DevBuf<int32_t> g, pf, g2, pf2, labels, land_cnt, land_cell, seg_frame, seg_label;
   DevBuf<double> land_tot, edges;
@@ -227,6 +254,10 @@ struct rpt_stack {
     DevBuf<int64_t>* i64[] = {&row_prefix, &file_off, &new_off, &first_noise, &seg_count,
                               &seg_first, &scal};
     for (auto* b : i64) b->release();
+    fo_d.release();
+    land_cell16.release();
+    v8.release();
+    v8b.release();
     DevBuf<float>* f32[] = {&x, &y, &v, &x2, &y2, &v2, &t, &seg_cx, &seg_cy, &seg_mi};
     for (auto* b : f32) b->release();
     DevBuf<int32_t>* i32[] = {&g,        &pf,       &g2,        &pf2,      &labels,

@@ -25,6 +25,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "frame_index.h"
 
 #pragma clang fp contract(off)
 
@@ -44,14 +45,15 @@ __global__ void k_sum_keys(const int32_t* __restrict__ labels, int64_t n,
 
 // head[p] = 1 where a (label, frame) run starts among clustered points; for the noise run, the
 // first noise point of each frame is recorded.
+template <class FR>
 __global__ void k_heads(const uint32_t* __restrict__ sk, const uint32_t* __restrict__ sv,
-                        const int32_t* __restrict__ pf, int64_t n, int32_t* __restrict__ head,
+                        FR fr, int64_t n, int32_t* __restrict__ head,
                         int64_t* __restrict__ first_noise) {
   for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n;
        p += (int64_t)gridDim.x * blockDim.x) {
     const uint32_t k = sk[p], i = sv[p];
-    const int32_t f = pf[i];
-    const bool h = (p == 0) || k != sk[p - 1] || f != pf[sv[p - 1]];
+    const int32_t f = fr.frame(i);
+    const bool h = (p == 0) || k != sk[p - 1] || f != fr.frame(sv[p - 1]);
     head[p] = (k != 0u && h) ? 1 : 0;
     if (k == 0u && h && first_noise) first_noise[f] = (int64_t)i;
   }
@@ -64,9 +66,25 @@ __global__ void k_seg_starts(const int32_t* __restrict__ head, const int32_t* __
     if (head[p]) seg_start[pos[p]] = p;
 }
 
-// numpy pairwise_sum over a[b .. b+len) (float32), iterative form of the recursion.  Only
-// reached when intensities are not small non-negative integers (see k_summarize).
-__device__ float pairwise_f32(const float* __restrict__ a, int64_t b, int64_t len) {
+// Intensities are float32 or -- the stack driver's narrow path, u8 echo samples -- uint8_t (the
+// kernels' VT): every read converts on load.
+__device__ __forceinline__ float to_float(float v) { return v; }
+__device__ __forceinline__ float to_float(uint8_t v) { return (float)v; }
+// four consecutive intensities at p + 4 q (p aligned to four elements)
+__device__ __forceinline__ float4 load4(const float* __restrict__ p, int q) {
+  return reinterpret_cast<const float4*>(p)[q];
+}
+__device__ __forceinline__ float4 load4(const uint8_t* __restrict__ p, int q) {
+  const uint32_t w = reinterpret_cast<const uint32_t*>(p)[q];
+  return make_float4((float)(w & 0xffu), (float)((w >> 8) & 0xffu), (float)((w >> 16) & 0xffu),
+                     (float)(w >> 24));
+}
+
+// numpy pairwise_sum over a[b .. b+len) (as float32), iterative form of the recursion.  Only
+// reached when intensities are not small non-negative integers, or their sum reaches 2^24 (see
+// k_summarize).
+template <class VT>
+__device__ float pairwise_f32(const VT* __restrict__ a, int64_t b, int64_t len) {
   int64_t sb[40], sl[40];
   int st[40];
   float vs[40];
@@ -79,20 +97,20 @@ __device__ float pairwise_f32(const float* __restrict__ a, int64_t b, int64_t le
     const int64_t bb = sb[sp - 1], ll = sl[sp - 1];
     if (ll < 8) {
       float r = 0.f;  // numpy: res = 0.; res += a[i]
-      for (int64_t i = 0; i < ll; ++i) r = r + a[bb + i];
+      for (int64_t i = 0; i < ll; ++i) r = r + to_float(a[bb + i]);
       --sp;
       vs[vp++] = r;
     } else if (ll <= 128) {
       float r[8];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) r[k] = a[bb + k];
+      for (int k = 0; k < 8; ++k) r[k] = to_float(a[bb + k]);
       int64_t i = 8;
       for (; i < ll - (ll % 8); i += 8) {
 #pragma unroll
-        for (int k = 0; k < 8; ++k) r[k] = r[k] + a[bb + i + k];
+        for (int k = 0; k < 8; ++k) r[k] = r[k] + to_float(a[bb + i + k]);
       }
       float res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-      for (; i < ll; ++i) res = res + a[bb + i];
+      for (; i < ll; ++i) res = res + to_float(a[bb + i]);
       --sp;
       vs[vp++] = res;
     } else {
@@ -122,10 +140,11 @@ __device__ float pairwise_f32(const float* __restrict__ a, int64_t b, int64_t le
 }
 
 // points of every run gathered contiguously (coalesced writes, one gather read per point)
+template <class VT>
 __global__ void k_gather_runs(const uint32_t* __restrict__ sv, int64_t n,
                               const float* __restrict__ x, const float* __restrict__ y,
-                              const float* __restrict__ inten, float* __restrict__ gx,
-                              float* __restrict__ gy, float* __restrict__ gi) {
+                              const VT* __restrict__ inten, float* __restrict__ gx,
+                              float* __restrict__ gy, VT* __restrict__ gi) {
   for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n;
        p += (int64_t)gridDim.x * blockDim.x) {
     const uint32_t i = sv[p];
@@ -277,9 +296,48 @@ __device__ __forceinline__ float seq_sum(const float* __restrict__ gx,
 // total stays below 2^24, every summation order is exact (integer lane sums), which equals
 // numpy's pairwise result; otherwise numpy's chunked pairwise sum is evaluated by lane 0.
 // 32 loads per lane in flight per round.
-__device__ __forceinline__ float mean_intensity(const float* __restrict__ gi, int b, int e,
+template <class VT>
+__device__ __forceinline__ float mean_intensity(const VT* __restrict__ gi, int b, int e,
                                                 int lane) {
   constexpr int kU = 32;
+  if constexpr (sizeof(VT) == 1) {
+    // u8 samples: numpy's 8192-element buffer chunks [b + 8192 c, ...) one after the other.  A
+    // chunk's pairwise float32 sum is its integer sum (every partial sum of at most 8192 values
+    // of at most 255 is an integer below 2^24, exact in float32 in any order), so the wave sums
+    // each chunk as integers -- whole 4-byte words, 32 per lane in flight (byte loads kept a
+    // quarter of the bytes in flight and made this wave the longer one of a run's two) -- and
+    // adds the chunks' sums in order, as np.add.reduce does; below 2^24 in total that chain is
+    // exact as well and the integer total is used.  gi's base is 4-byte aligned (scratch carve).
+    constexpr int kChunk = 8192;
+    static_assert(kChunk == 4 * 64 * kU, "one round of word loads covers a chunk");
+    uint64_t isum = 0;
+    float tot = 0.f;
+    for (int cb = b; cb < e; cb += kChunk) {
+      const int ce = min(e, cb + kChunk);
+      const int wb = min(ce, (cb + 3) & ~3);  // whole words [wb, we), at most 3 bytes either side
+      const int we = wb + ((ce - wb) & ~3);
+      uint32_t cs = 0;
+      if (cb + lane < wb) cs += gi[cb + lane];
+      if (we + lane < ce) cs += gi[we + lane];
+      const uint32_t* __restrict__ wp = reinterpret_cast<const uint32_t*>(gi + wb);
+      const int nw = (we - wb) >> 2;
+      uint32_t w[kU];
+#pragma unroll
+      for (int t = 0; t < kU; ++t) {
+        const int q = t * 64 + lane;
+        w[t] = q < nw ? wp[q] : 0u;
+      }
+#pragma unroll
+      for (int t = 0; t < kU; ++t)
+        cs += (w[t] & 0xffu) + ((w[t] >> 8) & 0xffu) + ((w[t] >> 16) & 0xffu) + (w[t] >> 24);
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) cs += __shfl_xor(cs, off);
+      isum += cs;
+      tot = tot + (float)cs;
+    }
+    const float fk8 = (float)(e - b);
+    return isum < 16777216u ? (float)isum / fk8 : tot / fk8;
+  }
   uint64_t isum = 0;
   bool small_int = true;
   for (int c0 = b; c0 < e; c0 += 64 * kU) {
@@ -287,7 +345,7 @@ __device__ __forceinline__ float mean_intensity(const float* __restrict__ gi, in
 #pragma unroll
     for (int t = 0; t < kU; ++t) {
       const int idx = c0 + t * 64 + lane;
-      v[t] = idx < e ? gi[idx] : 0.f;
+      v[t] = idx < e ? to_float(gi[idx]) : 0.f;
     }
 #pragma unroll
     for (int t = 0; t < kU; ++t) {
@@ -336,12 +394,12 @@ __device__ __forceinline__ void run_bounds(const int64_t* __restrict__ seg_start
 // (long_list / *n_long, zeroed beforehand) instead.  Every lane takes part in the wave-level
 // steps; lanes without a run of their own walk an empty range.
 constexpr int kLq = 8;  // float4 loads per column per block (32 points)
-template <bool META>
+template <bool META, class FR, class VT>
 __global__ __launch_bounds__(kBlock, 2) void k_runs_lane(
     const uint32_t* __restrict__ sk, const uint32_t* __restrict__ sv,
     const int64_t* __restrict__ seg_start, const int32_t* __restrict__ n_seg_dev, int64_t n,
-    const float* __restrict__ gx, const float* __restrict__ gy, const float* __restrict__ gi,
-    const int32_t* __restrict__ pf, int32_t* __restrict__ o_frame, int32_t* __restrict__ o_label,
+    const float* __restrict__ gx, const float* __restrict__ gy, const VT* __restrict__ gi,
+    FR fr, int32_t* __restrict__ o_frame, int32_t* __restrict__ o_label,
     int64_t* __restrict__ o_count, int64_t* __restrict__ o_first, float* __restrict__ o_cx,
     float* __restrict__ o_cy, float* __restrict__ o_mi, int32_t* __restrict__ long_list,
     int32_t* __restrict__ n_long) {
@@ -377,13 +435,13 @@ __global__ __launch_bounds__(kBlock, 2) void k_runs_lane(
     if (i < e) {
       ax = gx[i];
       ay = gy[i];
-      ivisit(gi[i], true);
+      ivisit(to_float(gi[i]), true);
       ++i;
     }
     for (; i < e && (i & 3); ++i) {
       ax = ax + gx[i];
       ay = ay + gy[i];
-      ivisit(gi[i], true);
+      ivisit(to_float(gi[i]), true);
     }
     // whole float4s [i, i + 4 nq) in blocks of kLq per column; the block loop runs to the wave's
     // largest block count with branch-free loads (a lane past its own blocks re-reads a valid
@@ -399,7 +457,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_runs_lane(
       const int last = nblk > 0 ? nblk - 1 : 0;
       const float4* __restrict__ px = reinterpret_cast<const float4*>(gx + i0);
       const float4* __restrict__ py = reinterpret_cast<const float4*>(gy + i0);
-      const float4* __restrict__ pi = reinterpret_cast<const float4*>(gi + i0);
+      const VT* __restrict__ pi = gi + i0;
       for (int k = 0; k < nbmax; ++k) {
         const int kk = min(k, last);
         float4 qx[kLq], qy[kLq], qi[kLq];
@@ -407,7 +465,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_runs_lane(
         for (int u = 0; u < kLq; ++u) {
           qx[u] = px[kk * kLq + u];
           qy[u] = py[kk * kLq + u];
-          qi[u] = pi[kk * kLq + u];
+          qi[u] = load4(pi, kk * kLq + u);
         }
         const bool on = k < nblk;
 #pragma unroll
@@ -431,7 +489,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_runs_lane(
     for (int q = nblk * kLq; q < nq; ++q) {
       const float4 vx = reinterpret_cast<const float4*>(gx + i)[q];
       const float4 vy = reinterpret_cast<const float4*>(gy + i)[q];
-      const float4 vi = reinterpret_cast<const float4*>(gi + i)[q];
+      const float4 vi = load4(gi + i, q);
       ax = ax + vx.x;
       ax = ax + vx.y;
       ax = ax + vx.z;
@@ -448,7 +506,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_runs_lane(
     for (i += 4 * nq; i < e; ++i) {
       ax = ax + gx[i];
       ay = ay + gy[i];
-      ivisit(gi[i], true);
+      ivisit(to_float(gi[i]), true);
     }
     if (mine) {
       const int k = e - b;
@@ -466,7 +524,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_runs_lane(
       o_mi[su] = mi;
       if (!META) {
         const uint32_t i0 = sv[b];
-        o_frame[su] = pf[i0];
+        o_frame[su] = fr.frame(i0);
         o_label[su] = (int32_t)sk[b] - 1;
         o_count[su] = k;
         o_first[su] = i0;
@@ -480,14 +538,16 @@ __global__ __launch_bounds__(kBlock, 2) void k_runs_lane(
 // index order; seq_sum) -- pure dependent-add chains, so no other work sits in their instruction
 // stream.  META: the frame sort already wrote frame/label/count/first; otherwise the metadata
 // comes from the sorted keys (written by the intensity wave).
-template <bool META>
+template <bool META, class FR, class VT>
 // 2 waves/SIMD (up to 256 VGPRs: the x and y prefetch registers and the chain's two register
 // windows; 4 waves spilled 17; a long run's waves are few, occupancy does not bound them)
-__global__ __launch_bounds__(kBlock, 2) void k_summarize(
+// (the radix path's u8 form, left to itself, takes 200 VGPRs -- 2 waves -- where its float form
+// takes 159: held to the float form's 3 waves, 168 VGPRs, no spill)
+__global__ __launch_bounds__(kBlock, (!META && sizeof(VT) == 1) ? 3 : 2) void k_summarize(
     const uint32_t* __restrict__ sk, const uint32_t* __restrict__ sv,
     const int64_t* __restrict__ seg_start, const int32_t* __restrict__ n_seg_dev, int64_t n,
-    const float* __restrict__ gx, const float* __restrict__ gy, const float* __restrict__ gi,
-    const int32_t* __restrict__ pf, int32_t* __restrict__ o_frame, int32_t* __restrict__ o_label,
+    const float* __restrict__ gx, const float* __restrict__ gy, const VT* __restrict__ gi,
+    FR fr, int32_t* __restrict__ o_frame, int32_t* __restrict__ o_label,
     int64_t* __restrict__ o_count, int64_t* __restrict__ o_first, float* __restrict__ o_cx,
     float* __restrict__ o_cy, float* __restrict__ o_mi, const int32_t* __restrict__ long_list,
     const int32_t* __restrict__ n_long_dev) {
@@ -512,7 +572,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_summarize(
         o_mi[su] = mi;
         if (!META) {
           const uint32_t i0 = sv[b];
-          o_frame[su] = pf[i0];
+          o_frame[su] = fr.frame(i0);
           o_label[su] = (int32_t)sk[b] - 1;
           o_count[su] = k;
           o_first[su] = i0;
@@ -704,6 +764,25 @@ __device__ __forceinline__ int64_t lower_bound_i32(const int32_t* __restrict__ a
   return lo;
 }
 
+// Where the frames' points lie in the frame-major point order, two forms (the kernels' FR):
+// per-point frame slots (the public call and the shard driver) or the frame offsets
+// off[0 .. F] of the same points (the stack driver's narrow path, which keeps no slots).
+// begin(n, f): first point of frame slot >= f, by the whole wave (uniform f, f <= F);
+// frame(i): frame slot of point i.
+struct FramesPf {
+  const int32_t* __restrict__ pf;
+  __device__ __forceinline__ int begin(int64_t n, int f) const {
+    return (int)lower_bound_i32(pf, n, f);
+  }
+  __device__ __forceinline__ int32_t frame(int64_t i) const { return pf[i]; }
+};
+struct FramesOff {
+  const int64_t* __restrict__ off;
+  int32_t F;
+  __device__ __forceinline__ int begin(int64_t, int f) const { return (int)off[f]; }
+  __device__ __forceinline__ int32_t frame(int64_t i) const { return frame_of_point(off, F, i); }
+};
+
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, int lane) {
 #pragma unroll
   for (int off = 1; off < 64; off <<= 1) {
@@ -715,18 +794,19 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, int lane) {
 
 // Per segment q of the frame the frame-local lists at [lo + q] get the run's start position,
 // length and label; tmp_first[start] gets the run's first point index.
+template <class FR, class VT>
 __global__ __launch_bounds__(kFsWaves * 64) void k_frame_sort(
-    const int32_t* __restrict__ labels, const int32_t* __restrict__ pf, int64_t n,
-    const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ inten,
-    float* __restrict__ gx, float* __restrict__ gy, float* __restrict__ gi,
+    const int32_t* __restrict__ labels, FR fr, int64_t n,
+    const float* __restrict__ x, const float* __restrict__ y, const VT* __restrict__ inten,
+    float* __restrict__ gx, float* __restrict__ gy, VT* __restrict__ gi,
     int32_t* __restrict__ fstart, int32_t* __restrict__ tmp_start, int32_t* __restrict__ tmp_len,
     int32_t* __restrict__ tmp_label, int32_t* __restrict__ tmp_first,
     int32_t* __restrict__ nseg_f, int64_t* __restrict__ first_noise,
     int32_t* __restrict__ overflow) {
   __shared__ FsLds L;
   const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int lo = __builtin_amdgcn_readfirstlane((int)lower_bound_i32(pf, n, f));
-  const int hi = __builtin_amdgcn_readfirstlane((int)lower_bound_i32(pf, n, f + 1));
+  const int lo = __builtin_amdgcn_readfirstlane(fr.begin(n, f));
+  const int hi = __builtin_amdgcn_readfirstlane(fr.begin(n, f + 1));
   for (int s = tid; s < kFsSlots; s += kFsWaves * 64) {
     L.keys[s] = -1;
 #pragma unroll
@@ -890,25 +970,27 @@ __global__ __launch_bounds__(kFsWaves * 64) void k_frame_sort(
 //                 k_frame_sort's pass 2.
 constexpr int kFsCap = kFsMaxKeys;  // entries per chunk list (more labels: overflow -> radix)
 
-__device__ __forceinline__ void fsc_chunk(const int32_t* __restrict__ pf, int64_t n, int C,
-                                          int b, int& f, int& lo, int& clo, int& chi) {
+template <class FR>
+__device__ __forceinline__ void fsc_chunk(FR fr, int64_t n, int C, int b, int& f, int& lo,
+                                          int& clo, int& chi) {
   f = b / C;
   const int c = b - f * C;
-  lo = __builtin_amdgcn_readfirstlane((int)lower_bound_i32(pf, n, f));
-  const int hi = __builtin_amdgcn_readfirstlane((int)lower_bound_i32(pf, n, f + 1));
+  lo = __builtin_amdgcn_readfirstlane(fr.begin(n, f));
+  const int hi = __builtin_amdgcn_readfirstlane(fr.begin(n, f + 1));
   const int64_t len = hi - lo;
   clo = lo + (int)(len * c / C);
   chi = lo + (int)(len * (c + 1) / C);
 }
 
+template <class FR>
 __global__ __launch_bounds__(kFsWaves * 64) void k_fsc_count(
-    const int32_t* __restrict__ labels, const int32_t* __restrict__ pf, int64_t n, int C,
+    const int32_t* __restrict__ labels, FR fr, int64_t n, int C,
     int32_t* __restrict__ ent_key, uint32_t* __restrict__ ent_cnt, int32_t* __restrict__ nent,
     int32_t* __restrict__ fnoise_c, int32_t* __restrict__ overflow) {
   __shared__ FsLds L;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   int f, lo, clo, chi;
-  fsc_chunk(pf, n, C, blockIdx.x, f, lo, clo, chi);
+  fsc_chunk(fr, n, C, blockIdx.x, f, lo, clo, chi);
   for (int s = tid; s < kFsSlots; s += kFsWaves * 64) {
     L.keys[s] = -1;
 #pragma unroll
@@ -1017,8 +1099,9 @@ __device__ int fsc_insert(FscLds& L, int v) {
   return -1;
 }
 
+template <class FR>
 __global__ __launch_bounds__(kFsWaves * 64) void k_fsc_merge(
-    const int32_t* __restrict__ pf, int64_t n, int C, const int32_t* __restrict__ ent_key,
+    FR fr, int64_t n, int C, const int32_t* __restrict__ ent_key,
     const uint32_t* __restrict__ ent_cnt, const int32_t* __restrict__ nent,
     const int32_t* __restrict__ fnoise_c, int32_t* __restrict__ ent_base,
     int32_t* __restrict__ ent_run, int32_t* __restrict__ fstart,
@@ -1027,7 +1110,7 @@ __global__ __launch_bounds__(kFsWaves * 64) void k_fsc_merge(
     int64_t* __restrict__ first_noise, int32_t* __restrict__ overflow) {
   __shared__ FscLds L;
   const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int lo = __builtin_amdgcn_readfirstlane((int)lower_bound_i32(pf, n, f));
+  const int lo = __builtin_amdgcn_readfirstlane(fr.begin(n, f));
   for (int s = tid; s < kFsSlots; s += kFsWaves * 64) {
     L.keys[s] = -1;
     L.tot[s] = 0u;
@@ -1127,10 +1210,11 @@ __global__ __launch_bounds__(kFsWaves * 64) void k_fsc_merge(
   }
 }
 
+template <class FR, class VT>
 __global__ __launch_bounds__(kFsWaves * 64) void k_fsc_scatter(
-    const int32_t* __restrict__ labels, const int32_t* __restrict__ pf, int64_t n, int C,
-    const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ inten,
-    float* __restrict__ gx, float* __restrict__ gy, float* __restrict__ gi,
+    const int32_t* __restrict__ labels, FR fr, int64_t n, int C,
+    const float* __restrict__ x, const float* __restrict__ y, const VT* __restrict__ inten,
+    float* __restrict__ gx, float* __restrict__ gy, VT* __restrict__ gi,
     int32_t* __restrict__ tmp_first, const int32_t* __restrict__ ent_key,
     const uint32_t* __restrict__ ent_cnt, const int32_t* __restrict__ nent,
     const int32_t* __restrict__ ent_base, const int32_t* __restrict__ ent_run,
@@ -1139,7 +1223,7 @@ __global__ __launch_bounds__(kFsWaves * 64) void k_fsc_scatter(
   if (*overflow) return;  // (block-uniform)
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   int f, lo, clo, chi;
-  fsc_chunk(pf, n, C, blockIdx.x, f, lo, clo, chi);
+  fsc_chunk(fr, n, C, blockIdx.x, f, lo, clo, chi);
   for (int s = tid; s < kFsSlots; s += kFsWaves * 64) L.keys[s] = -1;
   if (tid == 0) {
     L.nkeys = 0;
@@ -1164,7 +1248,8 @@ __global__ __launch_bounds__(kFsWaves * 64) void k_fsc_scatter(
   constexpr int U2 = 4;
   for (int cb = cb0; cb < cb1; cb += U2) {
     int lab[U2];
-    float px[U2], py[U2], pv[U2];
+    float px[U2], py[U2];
+    VT pv[U2];
 #pragma unroll
     for (int u = 0; u < U2; ++u) {
       const int i = clo + (cb + u) * 64 + lane;
@@ -1172,7 +1257,7 @@ __global__ __launch_bounds__(kFsWaves * 64) void k_fsc_scatter(
       lab[u] = in ? labels[i] : -2;
       px[u] = in ? x[i] : 0.f;
       py[u] = in ? y[i] : 0.f;
-      pv[u] = in ? inten[i] : 0.f;
+      pv[u] = in ? inten[i] : VT(0);
     }
 #pragma unroll
     for (int u = 0; u < U2; ++u) {
@@ -1245,8 +1330,9 @@ static int long_grid(int64_t s_hint) {
 
 // bits: radix bits of the label keys (label + 1 < 2^bits); s_hint: expected segment count (sizes
 // the summarize grid, which loops over the device count); *n_seg_dev: the count, on the device.
+template <class FR, class VT>
 static int32_t summaries_impl(const int32_t* labels, const float* x, const float* y,
-                              const float* inten, const int32_t* pf, int64_t n, int32_t n_frames,
+                              const VT* inten, FR pf, int64_t n, int32_t n_frames,
                               int bits, int64_t s_hint, int32_t* o_frame, int32_t* o_label,
                               int64_t* o_count, int64_t* o_first, float* o_cx, float* o_cy,
                               float* o_mi, int64_t* frame_first_noise,
@@ -1296,7 +1382,7 @@ static int32_t summaries_impl(const int32_t* labels, const float* x, const float
     RPT_TRY(sc.reserve(b.bytes, st));
     float* gx = sc.carve_n<float>(n + 1);
     float* gy = sc.carve_n<float>(n + 1);
-    float* gi = sc.carve_n<float>(n + 1);
+    VT* gi = sc.carve_n<VT>(n + 1);  // (budgeted as a float column: a u8 one needs less)
     int32_t* tstart = sc.carve_n<int32_t>(n + 1);
     int32_t* tlen = sc.carve_n<int32_t>(n + 1);
     int32_t* tlabel = sc.carve_n<int32_t>(n + 1);
@@ -1319,16 +1405,16 @@ static int32_t summaries_impl(const int32_t* labels, const float* x, const float
     }
     RPT_TRY(fill_noise(ovf));
     if (C == 1) {
-      hipLaunchKernelGGL(k_frame_sort, dim3(n_frames), dim3(kFsWaves * 64), 0, st, labels, pf, n,
+      hipLaunchKernelGGL((k_frame_sort<FR, VT>), dim3(n_frames), dim3(kFsWaves * 64), 0, st, labels, pf, n,
                          x, y, inten, gx, gy, gi, fstart, tstart, tlen, tlabel, tfirst, nseg_f,
                          frame_first_noise, ovf);
     } else {
-      hipLaunchKernelGGL(k_fsc_count, dim3((unsigned)NC), dim3(kFsWaves * 64), 0, st, labels, pf,
+      hipLaunchKernelGGL(k_fsc_count<FR>, dim3((unsigned)NC), dim3(kFsWaves * 64), 0, st, labels, pf,
                          n, C, ent_key, ent_cnt, nent, fnoise_c, ovf);
-      hipLaunchKernelGGL(k_fsc_merge, dim3(n_frames), dim3(kFsWaves * 64), 0, st, pf, n, C,
+      hipLaunchKernelGGL(k_fsc_merge<FR>, dim3(n_frames), dim3(kFsWaves * 64), 0, st, pf, n, C,
                          ent_key, ent_cnt, nent, fnoise_c, ent_base, ent_run, fstart, tstart,
                          tlen, tlabel, nseg_f, frame_first_noise, ovf);
-      hipLaunchKernelGGL(k_fsc_scatter, dim3((unsigned)NC), dim3(kFsWaves * 64), 0, st, labels,
+      hipLaunchKernelGGL((k_fsc_scatter<FR, VT>), dim3((unsigned)NC), dim3(kFsWaves * 64), 0, st, labels,
                          pf, n, C, x, y, inten, gx, gy, gi, tfirst, ent_key, ent_cnt, nent,
                          ent_base, ent_run, ovf);
     }
@@ -1340,11 +1426,11 @@ static int32_t summaries_impl(const int32_t* labels, const float* x, const float
     hipLaunchKernelGGL(k_seg_total_fix, dim3(1), dim3(64), 0, st, ovf, base + n_frames);
     // short runs one lane each; the long ones listed (in tlen, dead after the compaction) for
     // k_summarize's waves
-    hipLaunchKernelGGL(k_runs_lane<true>, dim3(grid_for((sh + 63) / 64, kBlock / 64, 4096)),
+    hipLaunchKernelGGL((k_runs_lane<true, FR, VT>), dim3(grid_for((sh + 63) / 64, kBlock / 64, 4096)),
                        dim3(kBlock), 0, st, nullptr, nullptr, seg_start, base + n_frames, n, gx,
                        gy, gi, pf, o_frame, o_label, o_count, o_first, o_cx, o_cy, o_mi, tlen,
                        ovf + 1);
-    hipLaunchKernelGGL(k_summarize<true>, dim3(long_grid(sh)), dim3(kBlock), 0, st, nullptr,
+    hipLaunchKernelGGL((k_summarize<true, FR, VT>), dim3(long_grid(sh)), dim3(kBlock), 0, st, nullptr,
                        nullptr, seg_start, base + n_frames, n, gx, gy, gi, pf, o_frame, o_label,
                        o_count, o_first, o_cx, o_cy, o_mi, tlen, ovf + 1);
     RPT_CHECK_LAUNCH();
@@ -1371,7 +1457,7 @@ static int32_t summaries_impl(const int32_t* labels, const float* x, const float
   int64_t* seg_start = sc.carve_n<int64_t>(n + 1);
   float* gx = sc.carve_n<float>(n + 1);
   float* gy = sc.carve_n<float>(n + 1);
-  float* gi = sc.carve_n<float>(n + 1);
+  VT* gi = sc.carve_n<VT>(n + 1);  // (budgeted as a float column)
   int32_t* n_long = sc.carve_n<int32_t>(1);
   if (n == 0) {
     RPT_HIP(hipMemsetAsync(pos, 0, sizeof(int32_t), st));
@@ -1384,17 +1470,17 @@ static int32_t summaries_impl(const int32_t* labels, const float* x, const float
   RPT_CHECK_LAUNCH();
   uint32_t *sk, *sv;
   RPT_TRY(radix_sort_pairs(keys, vals, ka, va, n, bits, rtmp, &sk, &sv, st));
-  hipLaunchKernelGGL(k_heads, dim3(g), dim3(kBlock), 0, st, sk, sv, pf, n, head,
+  hipLaunchKernelGGL(k_heads<FR>, dim3(g), dim3(kBlock), 0, st, sk, sv, pf, n, head,
                      frame_first_noise);
   RPT_TRY(exclusive_scan_total_i32(head, pos, n, st));
   hipLaunchKernelGGL(k_seg_starts, dim3(g), dim3(kBlock), 0, st, head, pos, n, seg_start);
-  hipLaunchKernelGGL(k_gather_runs, dim3(g), dim3(kBlock), 0, st, sv, n, x, y, inten, gx, gy, gi);
+  hipLaunchKernelGGL(k_gather_runs<VT>, dim3(g), dim3(kBlock), 0, st, sv, n, x, y, inten, gx, gy, gi);
   // short runs one lane each; the long ones listed (in head, dead after k_seg_starts)
   RPT_HIP(hipMemsetAsync(n_long, 0, sizeof(int32_t), st));
-  hipLaunchKernelGGL(k_runs_lane<false>, dim3(grid_for((sh + 63) / 64, kBlock / 64, 4096)),
+  hipLaunchKernelGGL((k_runs_lane<false, FR, VT>), dim3(grid_for((sh + 63) / 64, kBlock / 64, 4096)),
                      dim3(kBlock), 0, st, sk, sv, seg_start, pos + n, n, gx, gy, gi, pf, o_frame,
                      o_label, o_count, o_first, o_cx, o_cy, o_mi, head, n_long);
-  hipLaunchKernelGGL(k_summarize<false>, dim3(long_grid(sh)), dim3(kBlock), 0, st, sk, sv,
+  hipLaunchKernelGGL((k_summarize<false, FR, VT>), dim3(long_grid(sh)), dim3(kBlock), 0, st, sk, sv,
                      seg_start, pos + n, n, gx, gy, gi, pf, o_frame, o_label, o_count, o_first,
                      o_cx, o_cy, o_mi, head, n_long);
   RPT_CHECK_LAUNCH();
@@ -1423,7 +1509,8 @@ int32_t cluster_summaries(const int32_t* labels, const float* x, const float* y,
   const int32_t* nd = nullptr;
   int32_t n_seg = 0;
   for (int pass = 0; pass < 2; ++pass) {
-    RPT_TRY(summaries_impl(labels, x, y, inten, pf, n, n_frames, radix_bits_for(n_clusters),
+    RPT_TRY(summaries_impl(labels, x, y, inten, FramesPf{pf}, n, n_frames,
+                           radix_bits_for(n_clusters),
                            (int64_t)n_clusters * std::max(n_frames, 1) + 1, o_frame, o_label,
                            o_count, o_first, o_cx, o_cy, o_mi, frame_first_noise, &nd, pass == 1,
                            nullptr, st));
@@ -1439,19 +1526,28 @@ int32_t cluster_summaries(const int32_t* labels, const float* x, const float* y,
 // count (*n_seg_dev) with its other results after one sync.  A count of -1 means a frame held
 // more labels than the frame sort takes: redo with force_radix.  *radix_used tells whether the
 // label bits mattered (radix path) — the frame sort takes any labels.
+// frame_off (nullable; device, [n_frames + 1], frame_off[n_frames] = n): the points' frame
+// offsets instead of pf, which is then not read, together with inten8, the intensities as uint8_t
+// samples instead of inten (the stack driver's narrow path).
 int32_t cluster_summaries_dev(const int32_t* labels, const float* x, const float* y,
                               const float* inten, const int32_t* pf, int64_t n, int32_t n_frames,
                               int bits, int64_t s_hint, int32_t* o_frame, int32_t* o_label,
                               int64_t* o_count, int64_t* o_first, float* o_cx, float* o_cy,
                               float* o_mi, int64_t* frame_first_noise,
                               const int32_t** n_seg_dev, bool force_radix, bool* radix_used,
-                              hipStream_t st) {
-  if (n < 0 || n_frames < 0 || bits < 1 || bits > 32 || !n_seg_dev) {
+                              hipStream_t st, const int64_t* frame_off,
+                              const uint8_t* inten8) {
+  if (n < 0 || n_frames < 0 || bits < 1 || bits > 32 || !n_seg_dev ||
+      (frame_off != nullptr) != (inten8 != nullptr)) {
     set_error("cluster_summaries_dev: bad arguments");
     return RPT_EINVAL;
   }
-  return summaries_impl(labels, x, y, inten, pf, n, n_frames, bits, s_hint, o_frame, o_label,
-                        o_count, o_first, o_cx, o_cy, o_mi, frame_first_noise, n_seg_dev,
+  if (frame_off)
+    return summaries_impl(labels, x, y, inten8, FramesOff{frame_off, n_frames}, n, n_frames, bits,
+                          s_hint, o_frame, o_label, o_count, o_first, o_cx, o_cy, o_mi,
+                          frame_first_noise, n_seg_dev, force_radix, radix_used, st);
+  return summaries_impl(labels, x, y, inten, FramesPf{pf}, n, n_frames, bits, s_hint, o_frame,
+                        o_label, o_count, o_first, o_cx, o_cy, o_mi, frame_first_noise, n_seg_dev,
                         force_radix, radix_used, st);
 }
 
@@ -1507,7 +1603,7 @@ int32_t label_means(const int32_t* labels, const float* x, const float* y, const
   hipLaunchKernelGGL(k_label_heads, dim3(g), dim3(kBlock), 0, st, sk, n, head);
   RPT_TRY(exclusive_scan_total_i32(head, pos, n, st));
   hipLaunchKernelGGL(k_seg_starts, dim3(g), dim3(kBlock), 0, st, head, pos, n, seg_start);
-  hipLaunchKernelGGL(k_gather_runs, dim3(g), dim3(kBlock), 0, st, sv, n, x, y, inten, gx, gy, gi);
+  hipLaunchKernelGGL(k_gather_runs<float>, dim3(g), dim3(kBlock), 0, st, sv, n, x, y, inten, gx, gy, gi);
   hipLaunchKernelGGL(k_label_means, dim3(grid_for(3 * (n_labels + 1), kBlock / 64, 16384)),
                      dim3(kBlock), 0, st, sk, seg_start, pos + n, n, gx, gy, gi, n_labels,
                      o_count, o_x, o_y, o_v);
