@@ -30,6 +30,10 @@
  *   rpt_text_rows_write              and np.savetxt(fmt="%.6f,%.6f,%.6f,%d") of write_labels_csv :79-81;
  *                                    the float32 to_csv rows of convert_single_csv processors/cartesian.py:46-53
  *   rpt_float32_repr                 np.float32(v).astype(str) (host; the code of that layout)
+ *   rpt_segment_percentile99 /       normalize_intensity PointCloudWork/5_gain_fusion_ply_builder.py:276-289
+ *   rpt_heat_colors                  and intensity_to_rgb :292-327, per segment (frame) of one array;
+ *   (RPT_TEXT_PLY4)                  the np.savetxt rows of write_ply_fast :370-403
+ *   rpt_heat_host / rpt_fixed4_repr  the per-value code of those three on the host (no GPU)
  *   rpt_synth_echo                   (bench/test input generator; no reference counterpart)
  */
 #ifndef RPT_H
@@ -264,8 +268,14 @@ int32_t rpt_fuse_gains_max(const float* x, const float* y, const float* intensit
  * mantissa, the candidate nearest v among those of equal length), positional with ".0" / "0."
  * for 1e-4 <= |v| < 1e16 and zero, d[.ddd]e+XX otherwise; csrc/repr32.h has the rules.  At most
  * 19 bytes a value, 60 a row.  Domain: every finite value; a row holding NaN or inf is counted
- * in *n_unsupported_host (pandas writes an empty field / "inf": the host formatter's business). */
-enum { RPT_TEXT_PLY = 0, RPT_TEXT_LABELS = 1, RPT_TEXT_XYZ_REPR = 2 };
+ * in *n_unsupported_host (pandas writes an empty field / "inf": the host formatter's business).
+ *
+ *   RPT_TEXT_PLY4  "%.4f %.4f %.4f %d %d %d\n"  x, y, z f32 [n], tail = rgb u8 [n][3]
+ * the rows np.savetxt(fmt="%.4f %.4f %.4f %d %d %d") writes in write_ply_fast
+ * (PointCloudWork/5_gain_fusion_ply_builder.py:370-403): "%.4f" % float(np.float32(v)), half to even
+ * at the fourth decimal, "-0.0000" for -0.0 and negatives that round to zero.  Domain and
+ * *n_unsupported_host as for RPT_TEXT_PLY; at most 19 bytes a value, 72 a row. */
+enum { RPT_TEXT_PLY = 0, RPT_TEXT_LABELS = 1, RPT_TEXT_XYZ_REPR = 2, RPT_TEXT_PLY4 = 3 };
 int32_t rpt_text_rows_size(int32_t layout, const float* x, const float* y, const float* z,
                            const void* tail, int64_t n, int64_t* row_offsets /*dev [n+1]*/,
                            int64_t* total_host, int64_t* n_unsupported_host, void* stream);
@@ -278,6 +288,44 @@ int32_t rpt_text_rows_write(int32_t layout, const float* x, const float* y, cons
  * NaN and inf give len 0 and an all-NUL slot. */
 #define RPT_FLOAT32_REPR_SLOT 20
 int32_t rpt_float32_repr(const float* v, int64_t n, char* out /*[n][20]*/, int32_t* len /*[n]*/);
+
+/* ---- gain-fusion colours (5_gain_fusion_ply_builder.py normalize_intensity :276-289,
+ * intensity_to_rgb :292-327) ----------------------------------------------------------------
+ * v (dev, float32 [n]) is cut into n_seg segments by seg_off (dev, int64 [n_seg + 1],
+ * non-decreasing, seg_off[0] = 0, seg_off[n_seg] = n); a segment is one frame's intensities.
+ * n and n_seg < 2^31, else RPT_ENOTSUP.  No call synchronises.
+ *
+ * rpt_segment_percentile99: per segment np.min(seg) -> seg_min[s] and np.percentile(seg, 99) ->
+ * seg_p99[s] (dev, float32 [n_seg]), all in float32 as numpy evaluates them on a float32 array:
+ *   vi = float32(m - 1) * (float32(99) / float32(100));  lo = floor(vi);  hi = min(lo + 1, m - 1)
+ *   t = vi - lo;  a = sorted[lo];  b = sorted[hi];  d = b - a
+ *   p = t < 0.5 ? a + d * t : b - d * (1 - t)          (every operation rounded to float32)
+ * by a radix select (nothing is sorted).  Values order as floats of either sign (-0.0 below +0.0);
+ * NaNs are outside the contract.  An empty segment is legal; its outputs are unspecified.
+ *
+ * rpt_heat_colors: per point i of segment s
+ *   z[i] = clip((v[i] - seg_min[s]) / (seg_p99[s] - seg_min[s]) * 255.0, 0, 255)   (float32, IEEE
+ *          division), 0 for the whole segment when seg_p99[s] <= seg_min[s];
+ *   rgb[i] = the four-piece heat map of z[i]: normalized = z / 255.0 (a division) against 0.25 /
+ *          0.5 / 0.75, t = (normalized - k) * 4, channels (t * 255) and ((1 - t) * 255) truncated.
+ * z dev f32 [n], rgb dev u8 [n][3].  colors_only != 0: v is an already normalised z; only rgb is
+ * written and seg_off, seg_min, seg_p99 and z are not read (may be NULL).
+ *
+ * rpt_heat_host (host only, no GPU): both steps over host arrays by the same per-value code
+ * (csrc/heat.h); seg_min, seg_p99, z and rgb may each be NULL (not wanted).  RPT_EINVAL when the
+ * offsets are not those of v.
+ * rpt_fixed4_repr (host only): the "%.4f" text of RPT_TEXT_PLY4 per value, by the code the
+ * kernels run: out + RPT_FIXED4_SLOT * i holds the text padded with NULs, len[i] its length
+ * (<= 19); values outside the domain give len 0 and an all-NUL slot. */
+int32_t rpt_segment_percentile99(const float* v, int64_t n, const int64_t* seg_off, int64_t n_seg,
+                                 float* seg_min, float* seg_p99, void* stream);
+int32_t rpt_heat_colors(const float* v, int64_t n, const int64_t* seg_off, int64_t n_seg,
+                        const float* seg_min, const float* seg_p99, int32_t colors_only, float* z,
+                        uint8_t* rgb, void* stream);
+int32_t rpt_heat_host(const float* v, int64_t n, const int64_t* seg_off, int64_t n_seg,
+                      int32_t colors_only, float* seg_min, float* seg_p99, float* z, uint8_t* rgb);
+#define RPT_FIXED4_SLOT 20
+int32_t rpt_fixed4_repr(const float* v, int64_t n, char* out /*[n][20]*/, int32_t* len /*[n]*/);
 
 /* ---- K9: per-(frame, label) cluster summaries ---------------------------------------
  * point_frame[n] (dev, i32, non-decreasing frame slot per point), labels[n] from

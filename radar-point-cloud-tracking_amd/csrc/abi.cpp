@@ -330,7 +330,8 @@ int32_t rpt_infer_time_from_colors(const uint8_t* colors, int64_t n, const float
 }
 
 static bool text_layout_ok(int32_t layout) {
-  return layout == RPT_TEXT_PLY || layout == RPT_TEXT_LABELS || layout == RPT_TEXT_XYZ_REPR;
+  return layout == RPT_TEXT_PLY || layout == RPT_TEXT_LABELS || layout == RPT_TEXT_XYZ_REPR ||
+         layout == RPT_TEXT_PLY4;
 }
 
 int32_t rpt_text_rows_size(int32_t layout, const float* x, const float* y, const float* z,

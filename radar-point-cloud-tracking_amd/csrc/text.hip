@@ -21,7 +21,14 @@
 // "repr(x),repr(y),repr(z)\n" rows pandas' to_csv writes for float32 columns
 // (processors/cartesian.py:46-53), each value the shortest round-trip decimal of repr32.h (at most
 // 19 bytes, 60 a row).  Its domain is every finite value.
+//
+// A fourth, RPT_TEXT_PLY4, are the "%.4f %.4f %.4f %d %d %d\n" rows np.savetxt writes in
+// write_ply_fast (PointCloudWork/5_gain_fusion_ply_builder.py:370-403): the same integer method
+// with v * 10^4 = m * 625 * 2^(ex + 4) (fixed4 in heat.h, shared with the host), the same domain.
+// A value takes at most sign + 13 digits + '.' + 4 digits = 19 bytes, a row
+// 3 * 19 + 3 * 3 + 6 = 72.
 #include "common.h"
+#include "heat.h"
 #include "repr32.h"
 
 namespace rpt {
@@ -29,6 +36,9 @@ namespace {
 constexpr int kBlock = 256;
 // 3 * (sign + 13 digits + '.' + 6 digits) + 3 * (separator + up to 3 digits) + separators/newline
 constexpr int kRowMax = 81;
+constexpr int kRowMax4 = 3 * fixed4::kMaxLen + 3 * 3 + 6;  // RPT_TEXT_PLY4
+static_assert(kRowMax4 <= kRowMax && 3 * repr32::kMaxLen + 3 <= kRowMax,
+              "the staging buffer is sized by the longest row of any layout");
 constexpr int kStage = kBlock * kRowMax + 16;  // + the 16-byte phase of the block's first byte
 
 struct Dec {         // |v| * 10^6 rounded, as three base-10^6 limbs
@@ -132,9 +142,19 @@ struct ReprRow {
   int len;
 };
 
+struct Row4 {
+  fixed4::Dec c[3];
+  uint32_t t[3];  // r, g, b
+  int len;
+};
+
 template <int LAYOUT>
 struct RowOf {
   typedef Row type;
+};
+template <>
+struct RowOf<RPT_TEXT_PLY4> {
+  typedef Row4 type;
 };
 template <>
 struct RowOf<RPT_TEXT_XYZ_REPR> {
@@ -161,6 +181,40 @@ __device__ __forceinline__ void put_row(uint8_t* p, const ReprRow& r) {
   p = repr32::put(p, r.c[1]);
   *p++ = ',';
   p = repr32::put(p, r.c[2]);
+  *p = '\n';
+}
+
+template <int LAYOUT>
+__device__ __forceinline__ void load_row(const float* __restrict__ x, const float* __restrict__ y,
+                                         const float* __restrict__ z,
+                                         const void* __restrict__ tail, int64_t i, Row4* r) {
+  const bool okx = fixed4::decimal(__float_as_uint(x[i]), &r->c[0]);
+  const bool oky = fixed4::decimal(__float_as_uint(y[i]), &r->c[1]);
+  const bool okz = fixed4::decimal(__float_as_uint(z[i]), &r->c[2]);
+  const uint8_t* rgb = static_cast<const uint8_t*>(tail) + 3 * i;
+  r->t[0] = rgb[0];
+  r->t[1] = rgb[1];
+  r->t[2] = rgb[2];
+  // 5 spaces + newline
+  r->len = okx && oky && okz
+               ? ndigits(r->t[0]) + ndigits(r->t[1]) + ndigits(r->t[2]) + 6 +
+                     fixed4::length(r->c[0]) + fixed4::length(r->c[1]) + fixed4::length(r->c[2])
+               : -1;
+}
+
+template <int LAYOUT>
+__device__ __forceinline__ void put_row(uint8_t* p, const Row4& r) {
+  p = fixed4::put(p, r.c[0]);
+  *p++ = ' ';
+  p = fixed4::put(p, r.c[1]);
+  *p++ = ' ';
+  p = fixed4::put(p, r.c[2]);
+  *p++ = ' ';
+  p = put_u32(p, r.t[0]);
+  *p++ = ' ';
+  p = put_u32(p, r.t[1]);
+  *p++ = ' ';
+  p = put_u32(p, r.t[2]);
   *p = '\n';
 }
 
@@ -289,6 +343,9 @@ int32_t text_rows_size(int32_t layout, const float* x, const float* y, const flo
   else if (layout == RPT_TEXT_LABELS)
     hipLaunchKernelGGL(k_text_len<RPT_TEXT_LABELS>, grid, dim3(kBlock), 0, st, x, y, z, tail, n,
                        lens, n_bad);
+  else if (layout == RPT_TEXT_PLY4)
+    hipLaunchKernelGGL(k_text_len<RPT_TEXT_PLY4>, grid, dim3(kBlock), 0, st, x, y, z, tail, n,
+                       lens, n_bad);
   else
     hipLaunchKernelGGL(k_text_len<RPT_TEXT_XYZ_REPR>, grid, dim3(kBlock), 0, st, x, y, z, tail,
                        n, lens, n_bad);
@@ -314,6 +371,9 @@ int32_t text_rows_write(int32_t layout, const float* x, const float* y, const fl
                        row_offsets, out, out_bytes);
   else if (layout == RPT_TEXT_LABELS)
     hipLaunchKernelGGL(k_text_write<RPT_TEXT_LABELS>, grid, dim3(kBlock), 0, st, x, y, z, tail,
+                       n, row_offsets, out, out_bytes);
+  else if (layout == RPT_TEXT_PLY4)
+    hipLaunchKernelGGL(k_text_write<RPT_TEXT_PLY4>, grid, dim3(kBlock), 0, st, x, y, z, tail,
                        n, row_offsets, out, out_bytes);
   else
     hipLaunchKernelGGL(k_text_write<RPT_TEXT_XYZ_REPR>, grid, dim3(kBlock), 0, st, x, y, z, tail,

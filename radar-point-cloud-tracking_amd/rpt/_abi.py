@@ -25,7 +25,9 @@ ECHO_U8 = 1
 TEXT_PLY = 0
 TEXT_LABELS = 1
 TEXT_XYZ_REPR = 2
+TEXT_PLY4 = 3
 FLOAT32_REPR_SLOT = 20
+FIXED4_SLOT = 20
 
 c_f32p = C.POINTER(C.c_float)
 c_f64p = C.POINTER(C.c_double)
@@ -257,6 +259,11 @@ _SIGS = [
     ("rpt_text_rows_write", C.c_int32,
      [C.c_int32, vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int64, vp]),
     ("rpt_float32_repr", C.c_int32, [vp, C.c_int64, vp, vp]),
+    ("rpt_segment_percentile99", C.c_int32, [vp, C.c_int64, vp, C.c_int64, vp, vp, vp]),
+    ("rpt_heat_colors", C.c_int32,
+     [vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int32, vp, vp, vp]),
+    ("rpt_heat_host", C.c_int32, [vp, C.c_int64, vp, C.c_int64, C.c_int32, vp, vp, vp, vp]),
+    ("rpt_fixed4_repr", C.c_int32, [vp, C.c_int64, vp, vp]),
     ("rpt_csv_count_rows", C.c_int32, [C.POINTER(C.c_char_p), C.c_int32, c_i64p, C.c_int32]),
     ("rpt_csv_parse_sweeps", C.c_int32,
      [C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, c_f32p, c_f32p,

@@ -12,6 +12,11 @@ A third layout are the ``x,y,z`` rows ``DataFrame.to_csv`` writes for float32 co
 shortest decimal that reads back as the value (csrc/repr32.h).  The kernel covers every finite
 value; NaN (an empty field) and inf go to the host formatter, which is the pandas expression.
 
+A fourth are the ``"%.4f %.4f %.4f %d %d %d"`` rows ``np.savetxt`` writes in ``write_ply_fast``
+(PointCloudWork/5_gain_fusion_ply_builder.py:370-403): the ``"%.6f"`` method at four decimals
+(csrc/heat.h ``fixed4``), same domain, same host fallback.  ``ply4_rows_device`` also hands back
+the row offsets, so that one launch over a group of frames can be cut into one slice per file.
+
 Torch device tensors in -> a device ``uint8`` tensor out; numpy in -> ``bytes`` out.
 """
 from __future__ import annotations
@@ -27,6 +32,7 @@ from .._device import is_torch, stream_handle
 
 _HOST_CHUNK = 1 << 18      # rows per host-formatted piece
 _COPY_CHUNK = 1 << 25      # bytes per pinned staging buffer
+PLY4_ROW_MAX = 72          # 3 * (sign + 13 digits + '.' + 4 digits) + 3 * 3 colour digits + 6
 
 
 def gpu_visible() -> bool:
@@ -71,6 +77,22 @@ def format_label_rows_host(x, y, z, labels) -> bytes:
     return "".join(parts).encode()
 
 
+def format_ply4_rows_host(x, y, z, rgb) -> bytes:
+    """The rows of ``np.savetxt(fh, column_stack([x, y, z as float32, r, g, b as int]),
+    fmt="%.4f %.4f %.4f %d %d %d")`` (5_gain_fusion_ply_builder.py:391-401): every column promoted
+    to float64, ``%d`` of the colour."""
+    cols = [_np(a).astype(np.float32).astype(np.float64) for a in (x, y, z)]
+    c = _np(rgb)
+    cols += [c[:, k].astype(int) for k in range(3)]
+    n = len(cols[0])
+    parts = []
+    for lo in range(0, n, _HOST_CHUNK):
+        s = slice(lo, min(lo + _HOST_CHUNK, n))
+        parts.append("".join(["%.4f %.4f %.4f %d %d %d\n" % t
+                              for t in zip(*(c[s].tolist() for c in cols))]))
+    return "".join(parts).encode()
+
+
 def format_xyz_rows_host(x, y, z) -> bytes:
     """The body of ``pd.DataFrame({"x": x, "y": y, "z": z}).to_csv(index=False)``
     (cartesian.py:46-53): the text without its ``x,y,z`` header line."""
@@ -82,10 +104,10 @@ def format_xyz_rows_host(x, y, z) -> bytes:
 
 # ---- device formatter -------------------------------------------------------------------------
 
-def _device_rows(layout: int, x, y, z, tail) -> Optional[torch.Tensor]:
+def _device_rows(layout: int, x, y, z, tail, with_offsets: bool = False):
     """Rows of contiguous device tensors (x, y, z float32 [n]; tail uint8 [n][3], int32 [n] or
     None for the layout without one) as a device uint8 tensor, or None when a row is outside the
-    kernel's domain."""
+    kernel's domain.  with_offsets: (text, row offsets int64 [n + 1] on the device) instead."""
     dev = x.device
     n = x.numel()
     lib = _abi.load()
@@ -106,11 +128,14 @@ def _device_rows(layout: int, x, y, z, tail) -> Optional[torch.Tensor]:
                                            tail_ptr, n, offsets.data_ptr(),
                                            out.data_ptr(), out.numel(), st),
                    "rpt_text_rows_write")
-    return out
+    return (out, offsets) if with_offsets else out
+
+
+_RGB_LAYOUTS = (_abi.TEXT_PLY, _abi.TEXT_PLY4)
 
 
 def _tail_dtype(layout: int):
-    return (np.uint8, torch.uint8) if layout == _abi.TEXT_PLY else (np.int32, torch.int32)
+    return (np.uint8, torch.uint8) if layout in _RGB_LAYOUTS else (np.int32, torch.int32)
 
 
 def _device_ok(layout: int, x, y, z, tail) -> bool:
@@ -127,7 +152,7 @@ def _device_ok(layout: int, x, y, z, tail) -> bool:
     if layout == _abi.TEXT_XYZ_REPR:
         return True
     np_t, torch_t = _tail_dtype(layout)
-    want = (n, 3) if layout == _abi.TEXT_PLY else (n,)
+    want = (n, 3) if layout in _RGB_LAYOUTS else (n,)
     if tuple(tail.shape) != want:
         return False
     if is_torch(tail):
@@ -184,8 +209,20 @@ def format_xyz_rows(x, y, z, as_tensor: Optional[bool] = None):
     return _format(_abi.TEXT_XYZ_REPR, x, y, z, None, as_tensor)
 
 
+def format_ply4_rows(x, y, z, rgb, as_tensor: Optional[bool] = None):
+    """``"%.4f %.4f %.4f %d %d %d\\n"`` per point; as_tensor as for format_ply_rows."""
+    return _format(_abi.TEXT_PLY4, x, y, z, rgb, as_tensor)
+
+
+def ply4_rows_device(x, y, z, rgb):
+    """The ``"%.4f"`` rows of contiguous device tensors (x, y, z float32 [n], rgb uint8 [n][3]) as
+    (text uint8 [total], row offsets int64 [n + 1]), both on the device, or None when a coordinate
+    is outside the kernel's domain (the caller then formats on the host)."""
+    return _device_rows(_abi.TEXT_PLY4, x, y, z, rgb, with_offsets=True)
+
+
 _HOST = {_abi.TEXT_PLY: format_ply_rows_host, _abi.TEXT_LABELS: format_label_rows_host,
-         _abi.TEXT_XYZ_REPR: format_xyz_rows_host}
+         _abi.TEXT_XYZ_REPR: format_xyz_rows_host, _abi.TEXT_PLY4: format_ply4_rows_host}
 
 
 # ---- device text -> file ------------------------------------------------------------------------
@@ -232,3 +269,21 @@ def write_text(fh, text) -> None:
             events[k % 2].synchronize()
             fh.write(memoryview(bufs[k % 2].numpy())[:cnt])
             cnt = nxt
+
+
+def text_to_host(text: torch.Tensor) -> memoryview:
+    """A device text in host memory by ONE copy: through the first pinned staging buffer when it
+    fits there (the view is valid until the next call of this module that stages), else by a
+    pageable copy."""
+    n = text.numel()
+    if n == 0:
+        return memoryview(b"")
+    if not text.is_cuda:
+        return memoryview(text.numpy())
+    if n > _COPY_CHUNK:
+        return memoryview(text.cpu().numpy())
+    _, bufs = _staging(n, 1)
+    with torch.cuda.device(text.device):
+        bufs[0][:n].copy_(text, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+    return memoryview(bufs[0].numpy())[:n]

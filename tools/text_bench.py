@@ -1,17 +1,19 @@
 #!/usr/bin/env python3
 """Text-row formatter benchmark: device tensors -> file on disk, per layout.
 
-    python tools/text_bench.py [--rows 2000000] [--runs 3] [--legs labels,ply,xyz]
+    python tools/text_bench.py [--rows 2000000] [--runs 3] [--legs labels,ply,xyz,ply4]
                                [--out result.json]
 
-For each layout (labels CSV, PLY vertex lines, the x,y,z CSV of convert) the same seeded rows are
-written
+For each layout (labels CSV, PLY vertex lines, the x,y,z CSV of convert, the "%.4f" PLY rows of
+the gain-fusion builder) the same seeded rows are written
   device: rpt_text_rows_size + rpt_text_rows_write on the GPU, the text copied through pinned
           buffers into the file (what write_labels_csv / write_ply do when a GPU is visible);
   host:   labels: np.savetxt(fmt="%.6f,%.6f,%.6f,%d") on the host arrays -- write_labels_csv as it
           was before the formatter; PLY: the host formatter of rpt.core.text (the reference's
           expression), which write_ply uses without a GPU; xyz: the pandas expression of
-          convert_single_csv, DataFrame({"x", "y", "z"}).to_csv(path, index=False).
+          convert_single_csv, DataFrame({"x", "y", "z"}).to_csv(path, index=False); ply4:
+          np.savetxt(fmt="%.4f %.4f %.4f %d %d %d") on the column_stack write_ply_fast builds
+          (5_gain_fusion_ply_builder.py:391-401) -- the reference's own writer.
 The two are run alternately, `--runs` times each after one warm-up of the device path; medians and
 every single time are reported, the files are compared byte for byte, and the two kernels are
 timed alone with device events.  Needs a GPU: there is nothing to measure without one.
@@ -36,7 +38,8 @@ def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--rows", type=int, default=2_000_000)
     ap.add_argument("--runs", type=int, default=3)
-    ap.add_argument("--legs", default="labels,ply,xyz", help="comma-separated subset of the legs")
+    ap.add_argument("--legs", default="labels,ply,xyz,ply4",
+                    help="comma-separated subset of the legs")
     ap.add_argument("--dir", type=Path, default=None, help="where the files are written")
     ap.add_argument("--out", type=Path, default=None, help="also write the JSON result here")
     args = ap.parse_args()
@@ -92,6 +95,16 @@ def main() -> int:
 
         pd.DataFrame({"x": xyz[0], "y": xyz[1], "z": xyz[2]}).to_csv(path, index=False)
 
+    def device_ply4(path):
+        with open(path, "wb") as fh:
+            text.write_text(fh, text.format_ply4_rows(*d_xyz, d_rgb))
+
+    def host_ply4(path):
+        data = np.column_stack([xyz[0], xyz[1], xyz[2], rgb[:, 0].astype(int),
+                                rgb[:, 1].astype(int), rgb[:, 2].astype(int)])
+        with open(path, "w", encoding="utf-8") as fh:
+            np.savetxt(fh, data, fmt="%.4f %.4f %.4f %d %d %d")
+
     def timed(fn, path):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -131,7 +144,8 @@ def main() -> int:
     for name, dfn, hfn, layout, tail in (
             ("labels", device_labels, host_labels, _abi.TEXT_LABELS, d_labels),
             ("ply", device_ply, host_ply, _abi.TEXT_PLY, d_rgb),
-            ("xyz", device_xyz, host_xyz, _abi.TEXT_XYZ_REPR, None)):
+            ("xyz", device_xyz, host_xyz, _abi.TEXT_XYZ_REPR, None),
+            ("ply4", device_ply4, host_ply4, _abi.TEXT_PLY4, d_rgb)):
         if name not in legs:
             continue
         dp, hp = out_dir / f"{name}_device.txt", out_dir / f"{name}_host.txt"
