@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "k1_emit.h"
 
 #pragma clang fp contract(off)
 
@@ -392,13 +393,17 @@ __device__ __forceinline__ uint32_t kept_entry(const GroupLds& L,
   return ((uint32_t)k << 18) | ((uint32_t)bin << 8) | __builtin_amdgcn_ubfe(w, 8u * (bin & 3), 8u);
 }
 
-// Staged kept samples (nullable): when a group keeps at most kStageSlots samples the count pass
-// also stores them in in-group rank order, as kept_entry() words, in the group's slot of
-// kStageSlots words; the write pass then reads those instead of the group's 4 KiB of echo (one
-// read of the echo for the whole K1).  A group that keeps more (dense sweeps) is read from the
-// echo again by the write pass.
-constexpr int kStageSlots = 512;  // (256: +39 us K1 at 1000 frames, profiles/r6/ab_stage512/)
-// Slot position of in-group kept rank i in a staged group of `total` entries.  With stride 4 (the
+// Staged kept samples (nullable): the count pass also stores kept samples as kept_entry() words
+// in the group's slot of kStageSlots words (k1_emit.h); the write pass then reads those instead
+// of the group's 4 KiB of echo (one read of the echo for the whole K1).  A group that is not
+// staged (dense sweeps) is read from the echo again by the write pass.  Two layouts, chosen from
+// n_files alone (staged_emitted() below) and passed to the write kernels as a uniform flag:
+//   by rank  (k_group_count_u8<HI, true>, groups to waves in any order): a group that keeps at
+//            most kStageSlots samples stores ALL of them in in-group rank order; the write pass
+//            reads the emitted ones, every stride-th.
+//   emitted  (k_group_count_u8_files, a file's groups counted in order): a group that emits at
+//            most kStageSlots outputs stores exactly those, in output order.
+// Slot position (by rank) of in-group kept rank i in a staged group of `total` entries.  With stride 4 (the
 // reference's POINT_STRIDE) the ranks of each residue mod 4 are contiguous and the four residues
 // packed back to back in [0, total): the write pass reads every 4th rank from one residue, i.e.
 // consecutive entries, instead of one entry in four from every line of the slot, while the count
@@ -511,6 +516,148 @@ __global__ __launch_bounds__(kBlock) void k_group_count_u8(const uint8_t* __rest
   }
 }
 
+// Staged count pass, emitted layout: besides the group counts it leaves, per group, only the
+// entries the write pass will emit (a quarter of the kept samples at the reference's stride 4:
+// a quarter of the rank searches and of the stores, and the write pass reads consecutive
+// entries).  Which kept samples those are depends on the group's in-file rank, so a file's
+// groups are counted IN ORDER by one workgroup of W waves (gridDim.x = n_files): in round r wave
+// w takes group r * W + w of the file, and the rank of the file's kept samples before the round
+// is carried by the workgroup.  W > 1: every wave leaves its group total in LDS, one block
+// barrier follows and a wave's rank is the round's base plus the totals of the waves below it
+// (totals double-buffered by round parity: a wave a round ahead writes the other half, and it
+// can be no further ahead than that).  Every wave runs every round's barrier; a wave without a
+// group in a short last round contributes 0.  No wave waits for another workgroup.
+//
+// A group that emits m = 1 .. kStageSlots outputs (k1_emit.h emit_staged) gets exactly those m
+// kept_entry() words at positions 0 .. m-1 of its slot of kStageSlots words; the rest of the slot
+// is not written.  A group that emits more is left to the write pass's echo re-read.
+// The next round's rows are loaded before this round's are used (16 VGPRs).
+template <int W>
+struct CountTotals {
+  uint32_t t[2][W];
+};
+template <bool HI, int W>
+__global__ __launch_bounds__(64 * W) void k_group_count_u8_files(
+    const uint8_t* __restrict__ echo, GroupMap gm, uint32_t K, EmitStride es,
+    int32_t* __restrict__ group_count, uint32_t* __restrict__ entries) {
+  __shared__ GroupLds s_lds[W];
+  __shared__ CountTotals<W> s_tot;
+  const int lane = threadIdx.x & 63;
+  const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x / 64);
+  const uint32_t f = blockIdx.x;
+  const int64_t file_row0 = (int64_t)f * gm.rows;
+  const uint32_t n_rounds = (gm.gpf + W - 1) / W;
+  auto load_group = [&](uint32_t gi, u32x4 (&q)[kGroupRows]) -> int {  // gi: any value
+    const int r0 = (int)gi * kGroupRows;
+    const int nr = gi < gm.gpf ? min(kGroupRows, gm.rows - r0) : 0;
+#pragma unroll
+    for (int k = 0; k < kGroupRows; ++k)
+      // streamed once: non-temporal loads keep the echo out of L2's reuse set
+      q[k] = (k < nr) ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(
+                            echo + (file_row0 + r0 + k) * 1024 + lane * 16))
+                      : u32x4{0u, 0u, 0u, 0u};
+    return nr;
+  };
+  u32x4 nx[kGroupRows];
+  int nr_next = load_group(w, nx);
+  uint32_t rank = 0u;  // the file's kept samples before this round (W == 1: before this group)
+  for (uint32_t r = 0u; r < n_rounds; ++r) {
+    const uint32_t gi = r * W + w;
+    const int nr = nr_next;  // 0: no group for this wave in this (last) round
+    uint4 v[kGroupRows];
+#pragma unroll
+    for (int k = 0; k < kGroupRows; ++k) v[k] = make_uint4(nx[k].x, nx[k].y, nx[k].z, nx[k].w);
+    nr_next = load_group(gi + W, nx);
+    uint32_t m[kGroupRows];
+    int incl[kGroupRows];
+#pragma unroll
+    for (int k = 0; k < kGroupRows; ++k)
+      m[k] = (k < nr) ? mask16(keep_bits<HI>(v[k].x, K), keep_bits<HI>(v[k].y, K),
+                               keep_bits<HI>(v[k].z, K), keep_bits<HI>(v[k].w, K))
+                      : 0u;  // a zero sample is kept when T = -1: rows past nr keep nothing
+    // two rows per scan: a row's inclusive lane count is <= 1024, so the low and high halves
+    // of one 32-bit DPP scan never carry into each other (the pass is half VALU-bound: PMC)
+    static_assert(kGroupRows == 4, "rows are scanned in pairs");
+    uint32_t rb[kGroupRows + 1];
+    rb[0] = 0;
+#pragma unroll
+    for (int k = 0; k < kGroupRows; k += 2) {
+      const int pair = wave_incl_scan_dpp(__popc(m[k]) | (__popc(m[k + 1]) << 16));
+      incl[k] = pair & 0xffff;
+      incl[k + 1] = (int)((uint32_t)pair >> 16);
+      const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane(pair, 63);
+      rb[k + 1] = rb[k] + (tot & 0xffffu);
+      rb[k + 2] = rb[k + 1] + (tot >> 16);
+    }
+    const uint32_t total = rb[kGroupRows];
+    uint32_t my_rank = rank;
+    if constexpr (W > 1) {
+      const uint32_t par = r & 1u;
+      if (lane == 0) s_tot.t[par][w] = total;
+      __syncthreads();
+      uint32_t below = 0u, all = 0u;
+      static_assert(W <= 4, "the wave totals are summed as scalars");
+#pragma unroll
+      for (uint32_t j = 0u; j < (uint32_t)W; ++j) {
+        const uint32_t t = __builtin_amdgcn_readfirstlane(s_tot.t[par][j]);
+        below += j < w ? t : 0u;
+        all += t;
+      }
+      my_rank += below;
+      rank += all;
+    } else {
+      rank += total;
+    }
+    if (nr == 0) continue;  // wave-uniform; the barrier above is behind us
+    const EmitSpan sp = emit_span(my_rank, total, es);
+    const int64_t grp = (int64_t)f * gm.gpf + gi;
+    if (emit_staged(sp)) {  // wave-uniform
+      uint32_t* e = entries + grp * kStageSlots;
+      GroupLds& L = s_lds[w];
+      group_to_lds(L, lane, m, incl, v);
+      for (uint32_t j = (uint32_t)lane; j < sp.m; j += 64u)
+        e[j] = kept_entry(L, rb, sp.rank0 + j * es.stride);
+      wave_lds_sync();  // the slice is rewritten by the next group
+    }
+    if (lane == 0) group_count[grp] = (int32_t)total;
+  }
+}
+
+// Which layout a staged K1 uses.  The file-ordered pass has whole files (4 MiB at 4096 rows) as
+// its work units, ceil(n_files / 256) of them on the busiest of the 256 CUs: it streams the echo
+// 8 to 16 % faster than the by-rank pass when the CUs are evenly loaded and loses that, and more,
+// when they are not.  Count pass, file-ordered / by rank, us (profiles/r13/k1_file_order/):
+//   files   on the busiest CU / average   file-ordered   by rank
+//    375            2 / 1.46                   433          324
+//   1500            6 / 5.86                  1238         1326
+//   1794            8 / 7.01                  1716         1597
+//   2052            9 / 8.02                  1859         1900
+//   3000           12 / 11.72          2498 .. 2596   2835 .. 2899
+//   6000           24 / 23.44                 4853         5510
+// So: the emitted layout when the busiest CU has at most 1/19 more than the average, from the
+// smallest stack it was measured ahead at.
+constexpr int64_t kCus = 256;  // MI355X
+constexpr int64_t kEmittedMinFiles = 1500;
+inline int64_t busiest_cu_files(int64_t n_files) { return (n_files + kCus - 1) / kCus; }
+inline bool staged_emitted(int64_t n_files) {
+  return n_files >= kEmittedMinFiles && n_files * 20 >= busiest_cu_files(n_files) * kCus * 19;
+}
+
+// Waves per file of the file-ordered count pass: the most of 4, 2, 1 with every workgroup
+// resident at once (a CU holds 32 waves and 160 KiB of LDS, a wave's GroupLds is 5 KiB: 7
+// workgroups of 4 waves, 15 of 2, 31 of 1).  A second round of workgroups would start when the
+// first ends: a tail as long as a whole file (W = 4 at 3000 files: 2512 us for W = 2's 2498;
+// W = 1 there, 3000 of the 8192 wave slots: 2933).  More waves per file could only be resident
+// in stacks that take the by-rank layout (W = 8 and 16 at 375 files: 433 and 462 us).
+//   files on the busiest CU   6, 7 (n_files <= 1792)   8 .. 15 (<= 3840)   16 and more
+//   W                                4                       2               1
+// (emitted n_files: 1500 .. 1536, 1703 .. 1792 | 1946 .. 2048, 2189 .. 2304, ..., 2919 .. 3072,
+// ..., 3648 .. 3840 | 3892 .. 4096, ..., and every n_files from 4865 on)
+inline int count_waves_per_file(int64_t n_files) {
+  const int64_t per_cu = busiest_cu_files(n_files);
+  return per_cu <= 7 ? 4 : (per_cu <= 15 ? 2 : 1);
+}
+
 // file_offsets input: per file ceil(kept / stride) from the group prefix
 __global__ void k_file_counts_groups(const int64_t* __restrict__ gprefix, int64_t n_files,
                                      uint32_t gpf, int stride, int64_t* __restrict__ file_out) {
@@ -539,8 +686,10 @@ __global__ __launch_bounds__(kBlock, 8) void k_group_write_u8(
     const int64_t* __restrict__ gprefix, const int64_t* __restrict__ file_offsets,
     int files_per_frame, float* __restrict__ x, float* __restrict__ y, VT* __restrict__ val,
     int32_t* __restrict__ gain_out, int32_t* __restrict__ pf_out, int64_t cap,
-    const uint32_t* __restrict__ entries, const uint32_t* __restrict__ list = nullptr,
-    const uint32_t* __restrict__ list_n = nullptr, uint32_t* __restrict__ bpart = nullptr) {
+    const uint32_t* __restrict__ entries, bool emitted,
+    const uint32_t* __restrict__ list = nullptr, const uint32_t* __restrict__ list_n = nullptr,
+    uint32_t* __restrict__ bpart = nullptr) {
+  // emitted (kernel-uniform; STAGED only): the entries' layout, see "Staged kept samples"
   // bpart (nullable, kernel-uniform): this block's xy-bounds partial (XyBounds)
   __shared__ GroupLds s_lds[kWavesPerBlock];
   XyBounds xb;
@@ -549,8 +698,7 @@ __global__ __launch_bounds__(kBlock, 8) void k_group_write_u8(
   const uint32_t wave0 = blockIdx.x * kWavesPerBlock + threadIdx.x / 64;
   const uint32_t n_waves = gridDim.x * kWavesPerBlock;
   const uint32_t us = (uint32_t)stride;
-  const bool pow2 = (us & (us - 1u)) == 0u;
-  const uint32_t sh = (uint32_t)__builtin_ctz(us);
+  const EmitStride es = emit_stride(us);
   const float inv_bins = 1.0f / 1024.0f;  // exact: step = scale / 1024 == scale * 2^-10
   const uint32_t n_items = LIST ? *list_n : n_groups;
   for (uint32_t g0 = wave0; g0 < n_items; g0 += n_waves) {
@@ -579,13 +727,14 @@ __global__ __launch_bounds__(kBlock, 8) void k_group_write_u8(
     const int64_t gp0 = gprefix[grp];
     const uint32_t rank = (uint32_t)(gp0 - gprefix[(int64_t)f * gm.gpf]);
     const uint32_t total = (uint32_t)(gprefix[grp + 1] - gp0);
-    const uint32_t first = pow2 ? ((rank + us - 1u) >> sh) : (rank + us - 1u) / us;
-    const uint32_t last = pow2 ? ((rank + total + us - 1u) >> sh) : (rank + total + us - 1u) / us;
-    if (last == first) continue;  // wave-uniform: nothing emitted
+    const EmitSpan sp = emit_span(rank, total, es);
+    if (sp.m == 0u) continue;  // wave-uniform: nothing emitted
+    const uint32_t first = sp.first, last = sp.first + sp.m;
     const int64_t out0 = file_offsets[f];
     const int32_t g = gain ? gain[f] : 0;
     const int32_t fr = (int32_t)(f / (uint32_t)files_per_frame);
-    const bool staged = STAGED && total <= (uint32_t)kStageSlots;
+    const bool staged =
+        STAGED && (emitted ? emit_staged(sp) : total <= (uint32_t)kStageSlots);  // wave-uniform
     uint32_t rb[kGroupRows + 1];
     if (!staged) {
       uint4 vv[kGroupRows];
@@ -612,8 +761,10 @@ __global__ __launch_bounds__(kBlock, 8) void k_group_write_u8(
     for (uint32_t o = first + (uint32_t)lane; o < last; o += 64u) {
       const int64_t oo = out0 + o;
       if (oo >= cap) break;
-      const uint32_t i = o * us - rank;  // in-group kept rank
-      const uint32_t ent = staged ? e[stage_pos(i, total, us == 4u)] : kept_entry(L, rb, i);
+      const uint32_t i = sp.rank0 + (o - first) * us;  // in-group kept rank
+      const uint32_t ent = !staged  ? kept_entry(L, rb, i)
+                           : emitted ? e[o - first]
+                                     : e[stage_pos(i, total, us == 4u)];
       const int rk = (int)(ent >> 18);
       const float sc = rk == 0 ? r_sc[0] : (rk == 1 ? r_sc[1] : (rk == 2 ? r_sc[2] : r_sc[3]));
       const float cc = rk == 0 ? r_c[0] : (rk == 1 ? r_c[1] : (rk == 2 ? r_c[2] : r_c[3]));
@@ -640,9 +791,12 @@ __global__ __launch_bounds__(kBlock, 8) void k_group_write_u8(
 // prefix -> entry -> store chain per group; its time is that chain times the groups per wave
 // slot.  Here the outputs themselves are spread over the threads: per group one 64-bit word
 //   bits 0..39  gs    = global index of the group's first emitted output
-//   bits 40..62 phase = in-group kept rank of that output (first * stride - rank < stride)
-//   bit 63      the group emits outputs but kept > kStageSlots samples (not staged): its
-//               outputs are written by k_group_write_u8<.., LIST> over the list of such groups
+//   bits 40..62 phase = slot position of that output's entry: 0 in the emitted layout (output
+//               gs + d is entry d, for every stride); by rank its in-group kept rank
+//               (first * stride - rank < stride), or its residue's base at stride 4
+//   bit 63      the group emits outputs but is not staged (emitted layout: more than kStageSlots
+//               outputs, emit_staged; by rank: more than kStageSlots kept samples): they are
+//               written by k_group_write_u8<.., LIST> over the list of such groups
 // and a block walks a contiguous range of 1024-output tiles, finding each output's group by a
 // binary search of an LDS window of those words (gs is non-decreasing in the group index).
 constexpr int kGsBits = 40;
@@ -656,7 +810,7 @@ constexpr int kWin = 1024;  // groups in the LDS window
 __global__ __launch_bounds__(kBlock) void k_group_starts(const int64_t* __restrict__ gprefix,
                                                         const int64_t* __restrict__ file_offsets,
                                                         uint32_t n_groups, uint32_t gpf,
-                                                        uint32_t stride,
+                                                        uint32_t stride, bool emitted,
                                                         uint64_t* __restrict__ gword,
                                                         uint32_t* __restrict__ list,
                                                         uint32_t* __restrict__ list_n) {
@@ -668,26 +822,25 @@ __global__ __launch_bounds__(kBlock) void k_group_starts(const int64_t* __restri
   __shared__ uint32_t s_n, s_base;
   if (threadIdx.x == 0) s_n = 0u;
   __syncthreads();
-  // power-of-two strides (the reference's 4) by shifts instead of 64-bit divisions
-  const bool pow2 = (stride & (stride - 1u)) == 0u;
-  const uint32_t sh = (uint32_t)__builtin_ctz(stride);
+  // power-of-two strides (the reference's 4) by shifts instead of divisions
+  const EmitStride es = emit_stride(stride);
   for (uint32_t b0 = blockIdx.x * kBlock; b0 < n_groups; b0 += gridDim.x * kBlock) {
     const uint32_t g = b0 + threadIdx.x;
     if (g < n_groups) {
       const uint32_t f = g / gpf;
       const int64_t p0 = gprefix[g];
-      const uint64_t rank = (uint64_t)(p0 - gprefix[(int64_t)f * gpf]);
-      const uint64_t total = (uint64_t)(gprefix[g + 1] - p0);
-      const uint64_t first = pow2 ? ((rank + stride - 1u) >> sh) : (rank + stride - 1u) / stride;
-      const uint64_t last =
-          pow2 ? ((rank + total + stride - 1u) >> sh) : (rank + total + stride - 1u) / stride;
-      const uint64_t gs = (uint64_t)file_offsets[f] + first;
-      // slot position of the first emitted output's entry: its in-group rank, or with stride 4
-      // (residues packed, stage_pos) the base of its residue
-      const uint64_t ph = first * stride - rank;
-      const uint64_t phase = stride == 4u ? (uint64_t)phase_base((uint32_t)ph, (uint32_t)total)
-                                          : ph;
-      const bool un = last > first && total > (uint64_t)kStageSlots;
+      // in-file rank and kept count: a file has fewer than 2^32 samples
+      const uint32_t rank = (uint32_t)(p0 - gprefix[(int64_t)f * gpf]);
+      const uint32_t total = (uint32_t)(gprefix[g + 1] - p0);
+      const EmitSpan sp = emit_span(rank, total, es);
+      const uint64_t gs = (uint64_t)file_offsets[f] + sp.first;
+      // slot position of the first emitted output's entry.  Emitted layout: 0.  By rank: its
+      // in-group rank, or with stride 4 (residues packed, stage_pos) the base of its residue
+      const uint64_t phase = emitted       ? 0ull
+                             : stride == 4u ? (uint64_t)phase_base(sp.rank0, total)
+                                            : (uint64_t)sp.rank0;
+      const bool un =
+          sp.m != 0u && !(emitted ? emit_staged(sp) : total <= (uint32_t)kStageSlots);
       gword[g] = gs | (phase << kGsBits) | (un ? kUnstaged : 0ull);
       if (un) {
         const uint32_t slot = atomicAdd(&s_n, 1u);
@@ -747,7 +900,7 @@ __device__ __forceinline__ uint32_t lds_find(const uint64_t* s_win, uint32_t wn,
 // VT: as k_group_write_u8's (uint8_t: a thread's four intensities are one 4-byte store)
 template <bool VEC, class VT = float>
 __global__ __launch_bounds__(kBlock) void k_expand_write(
-    const uint64_t* __restrict__ gword, uint32_t n_groups, GroupMap gm, uint32_t stride,
+    const uint64_t* __restrict__ gword, uint32_t n_groups, GroupMap gm, uint32_t estep,
     const float* __restrict__ scale, const float* __restrict__ cos_t,
     const float* __restrict__ sin_t, const int32_t* __restrict__ gain,
     const int64_t* __restrict__ total_out, int files_per_frame, float* __restrict__ x,
@@ -825,9 +978,10 @@ __global__ __launch_bounds__(kBlock) void k_expand_write(
         ok[k] = in && !(w & kUnstaged);
         grp[k] = g;
         // the entry's slot position, mod 2^32 like the 64-bit form (only staged groups use it:
-        // idx < kStageSlots): consecutive outputs are consecutive entries with stride 4
+        // idx < kStageSlots).  estep, the entries from one output to the next: 1 in the emitted
+        // layout and by rank at stride 4 (residues packed), else the stride
         const uint32_t d = (uint32_t)O - (uint32_t)w;
-        idx[k] = (stride == 4u ? d : d * stride) + (uint32_t)((w & ~kUnstaged) >> kGsBits);
+        idx[k] = d * estep + (uint32_t)((w & ~kUnstaged) >> kGsBits);
       }
     } else {
 #pragma unroll
@@ -988,7 +1142,22 @@ int32_t count_impl(const T* echo, int64_t n_files, int rows, int bins, float thr
 #define RPT_K1C(HI, S)                                                                    \
   hipLaunchKernelGGL((k_group_count_u8<HI, S>), dim3(grid), dim3(kBlock), 0, st, e8,        \
                      (uint32_t)n_units, gm, u8_k(T8), rc, entries, stride == 4 ? 1 : 0)
-    if (entries) {
+// one workgroup of W waves per file (n_files < 2^32 / rows: a valid grid size)
+#define RPT_K1F(HI, W)                                                                    \
+  hipLaunchKernelGGL((k_group_count_u8_files<HI, W>), dim3((unsigned)n_files), dim3(64 * W), 0, \
+                     st, e8, gm, u8_k(T8), emit_stride((uint32_t)stride), rc, entries)
+#define RPT_K1FW(W)       \
+  if (T8 <= 127)          \
+    RPT_K1F(false, W);    \
+  else                    \
+    RPT_K1F(true, W)
+    if (entries && staged_emitted(n_files)) {
+      switch (count_waves_per_file(n_files)) {
+        case 4: RPT_K1FW(4); break;
+        case 2: RPT_K1FW(2); break;
+        default: RPT_K1FW(1); break;
+      }
+    } else if (entries) {
       if (T8 <= 127)
         RPT_K1C(false, true);
       else
@@ -998,6 +1167,8 @@ int32_t count_impl(const T* echo, int64_t n_files, int rows, int bins, float thr
     } else {
       RPT_K1C(true, false);
     }
+#undef RPT_K1FW
+#undef RPT_K1F
 #undef RPT_K1C
   } else if (vec) {
     hipLaunchKernelGGL((k_row_count<T, true>), dim3(grid), dim3(kBlock), 0, st, echo, n_rows,
@@ -1047,6 +1218,7 @@ int32_t write_impl(const T* echo, int64_t n_files, int rows, int bins, float thr
     const int grid = grid_for(n_groups, kWavesPerBlock, 16384);
     const int T8 = u8_threshold(thr);
     const auto* e8 = reinterpret_cast<const uint8_t*>(echo);
+    const bool emitted = staged_emitted(n_files);  // the entries' layout, as the count pass
     if (entries && ab().k1_expand && stride < (1 << 23) &&
         n_files * (int64_t)rows * 1024 < (int64_t(1) << kGsBits)) {
       // staged entries: outputs to threads (k_expand_write); the few unstaged groups listed by
@@ -1062,27 +1234,28 @@ int32_t write_impl(const T* echo, int64_t n_files, int rows, int bins, float thr
       RPT_TRY(zero_n(st, 1, &list_n));
       hipLaunchKernelGGL(k_group_starts, dim3(grid_for(n_groups, kBlock, 4096)), dim3(kBlock), 0,
                          st, row_prefix, file_offsets, (uint32_t)n_groups, gm.gpf,
-                         (uint32_t)stride, gword, list, list_n);
+                         (uint32_t)stride, emitted, gword, list, list_n);
       RPT_CHECK_LAUNCH();
       auto al16 = [](const void* q) { return ((uintptr_t)q & 15u) == 0; };
       const bool vec4 = al16(x) && al16(y) && al16(v) && (!gout || al16(gout)) && (!pf || al16(pf));
+      const uint32_t estep = (emitted || stride == 4) ? 1u : (uint32_t)stride;
       if (vec4)
         hipLaunchKernelGGL((k_expand_write<true, VT>), dim3(kExpandBlocks), dim3(kBlock), 0, st, gword,
-                           (uint32_t)n_groups, gm, (uint32_t)stride, geo.scale, geo.cos_t,
-                           geo.sin_t, gain, file_offsets + n_files, fpf, x, y, v, gout, pf, cap,
-                           entries, bnd ? bnd + 4 : nullptr);
+                           (uint32_t)n_groups, gm, estep, geo.scale, geo.cos_t, geo.sin_t, gain,
+                           file_offsets + n_files, fpf, x, y, v, gout, pf, cap, entries,
+                           bnd ? bnd + 4 : nullptr);
       else
         hipLaunchKernelGGL((k_expand_write<false, VT>), dim3(kExpandBlocks), dim3(kBlock), 0, st,
-                           gword, (uint32_t)n_groups, gm, (uint32_t)stride, geo.scale, geo.cos_t,
-                           geo.sin_t, gain, file_offsets + n_files, fpf, x, y, v, gout, pf, cap,
-                           entries, bnd ? bnd + 4 : nullptr);
+                           gword, (uint32_t)n_groups, gm, estep, geo.scale, geo.cos_t, geo.sin_t,
+                           gain, file_offsets + n_files, fpf, x, y, v, gout, pf, cap, entries,
+                           bnd ? bnd + 4 : nullptr);
       RPT_CHECK_LAUNCH();
       const int lgrid = std::min(grid, kListBlocks);
 #define RPT_K1L(HI)                                                                            \
   hipLaunchKernelGGL((k_group_write_u8<HI, false, true, VT>), dim3(lgrid), dim3(kBlock), 0, st, e8, \
                      (uint32_t)n_groups, gm, u8_k(T8), stride, geo.scale, geo.cos_t, geo.sin_t,  \
-                     gain, row_prefix, file_offsets, fpf, x, y, v, gout, pf, cap, entries, list, \
-                     list_n, bnd ? bnd + 4 + 4 * kExpandBlocks : nullptr)
+                     gain, row_prefix, file_offsets, fpf, x, y, v, gout, pf, cap, entries,       \
+                     emitted, list, list_n, bnd ? bnd + 4 + 4 * kExpandBlocks : nullptr)
       if (T8 <= 127)
         RPT_K1L(false);
       else
@@ -1099,7 +1272,7 @@ int32_t write_impl(const T* echo, int64_t n_files, int rows, int bins, float thr
 #define RPT_K1W(HI, M)                                                                       \
   hipLaunchKernelGGL((k_group_write_u8<HI, M, false, VT>), dim3(grid), dim3(kBlock), 0, st, e8,          \
                      (uint32_t)n_groups, gm, u8_k(T8), stride, geo.scale, geo.cos_t, geo.sin_t, \
-                     gain, row_prefix, file_offsets, fpf, x, y, v, gout, pf, cap, entries)
+                     gain, row_prefix, file_offsets, fpf, x, y, v, gout, pf, cap, entries, emitted)
     if (entries) {
       if (T8 <= 127)
         RPT_K1W(false, true);
