@@ -104,13 +104,15 @@ int32_t rpt_polar_write(const void* echo, int32_t echo_dtype, int64_t n_files, i
                         void* stream);
 /* Same two passes with the kept samples staged between them (u8 sweeps of 1024 bins with 16-B
  * aligned rows; other sweeps ignore the buffer): for groups of 4 rows the count pass stores kept
- * samples as 32-bit (row, bin, sample) entries in the group's slot of 512 words of entries (dev,
- * rpt_polar_stage_words(n_files, rows) words), and the write pass reads those instead of the
- * group's echo -- one read of the echo for sparse sweeps (what rpt_stack_run does).  Which
- * groups are staged, and what a slot holds, is the library's choice from n_files: in large
- * stacks whose files spread evenly over the device a file's groups are counted in file order and
- * a group that emits 1 to 512 points stores exactly those, in output order; otherwise a group
- * that keeps 1 to 512 samples stores all of them.  The rest of a slot is not written, other
+ * samples as 32-bit (row, bin, sample) entries in entries (dev, rpt_polar_stage_words(n_files,
+ * rows) words: 512 per group), and the write pass reads those instead of the group's echo --
+ * one read of the echo for sparse sweeps (what rpt_stack_run does).  Which groups are staged,
+ * and where, is the library's choice from n_files and rows.  In large stacks whose files spread
+ * evenly over the device (sweeps of at most 16384 rows) a file's groups are counted in file
+ * order and the file's emitted points are stored, exactly those and in output order, as one
+ * dense array at the head of the file's ceil(rows / 4) * 512 words: every group up to the first
+ * one whose points would end beyond those words.  Otherwise a group has a slot of 512 words and
+ * one that keeps 1 to 512 samples stores all of them.  No other word is written, the remaining
  * groups are read from the echo again, and the buffer means nothing to the caller: pass the same
  * n_files, rows, threshold and stride to both calls.  Same outputs as rpt_polar_count +
  * rpt_polar_write. */

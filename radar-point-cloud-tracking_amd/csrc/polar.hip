@@ -394,15 +394,22 @@ __device__ __forceinline__ uint32_t kept_entry(const GroupLds& L,
 }
 
 // Staged kept samples (nullable): the count pass also stores kept samples as kept_entry() words
-// in the group's slot of kStageSlots words (k1_emit.h); the write pass then reads those instead
+// in a buffer of kStageSlots words per group (k1_emit.h); the write pass then reads those instead
 // of the group's 4 KiB of echo (one read of the echo for the whole K1).  A group that is not
 // staged (dense sweeps) is read from the echo again by the write pass.  Two layouts, chosen from
-// n_files alone (staged_emitted() below) and passed to the write kernels as a uniform flag:
-//   by rank  (k_group_count_u8<HI, true>, groups to waves in any order): a group that keeps at
-//            most kStageSlots samples stores ALL of them in in-group rank order; the write pass
-//            reads the emitted ones, every stride-th.
-//   emitted  (k_group_count_u8_files, a file's groups counted in order): a group that emits at
-//            most kStageSlots outputs stores exactly those, in output order.
+// n_files and rows alone (k1_emit.h staged_emitted()), the same in the count and the write call:
+//   by rank  (k_group_count_u8<HI, true>, groups to waves in any order): a group has a slot of
+//            kStageSlots words; one that keeps at most kStageSlots samples stores ALL of them in
+//            in-group rank order, and the write pass (k_group_starts + k_expand_write) reads the
+//            emitted ones, every stride-th.
+//   emitted, file-contiguous  (k_group_count_u8_files, a file's groups counted in order): file f
+//            has the C = gpf * kStageSlots words from f * C on.  A group that emits the file's
+//            outputs [first, first + m), m != 0 and first + m <= C (emit_staged_file), stores
+//            exactly those m entries at words first .. first + m - 1: the region is the file's
+//            outputs in order, word o = output o, global slot file_offsets[f] + o.  The entry's
+//            row field is the row within the FILE (14 bits; its low two bits are still the row
+//            within the group).  Nothing else is written to the buffer.  The write pass
+//            (k_file_staged + k_expand_stream) streams the regions: no per-group search.
 // Slot position (by rank) of in-group kept rank i in a staged group of `total` entries.  With stride 4 (the
 // reference's POINT_STRIDE) the ranks of each residue mod 4 are contiguous and the four residues
 // packed back to back in [0, total): the write pass reads every 4th rank from one residue, i.e.
@@ -528,9 +535,11 @@ __global__ __launch_bounds__(kBlock) void k_group_count_u8(const uint8_t* __rest
 // can be no further ahead than that).  Every wave runs every round's barrier; a wave without a
 // group in a short last round contributes 0.  No wave waits for another workgroup.
 //
-// A group that emits m = 1 .. kStageSlots outputs (k1_emit.h emit_staged) gets exactly those m
-// kept_entry() words at positions 0 .. m-1 of its slot of kStageSlots words; the rest of the slot
-// is not written.  A group that emits more is left to the write pass's echo re-read.
+// A group whose outputs [first, first + m) end inside the file's region of C = gpf * kStageSlots
+// words (k1_emit.h emit_staged_file) stores exactly those m kept_entry() words, with the group's
+// first row added to the row field, at words first .. first + m - 1 of the region: a file's
+// stores are one contiguous run in output order.  The groups from the first one that does not
+// fit are left to the write pass's echo re-read.
 // The next round's rows are loaded before this round's are used (16 VGPRs).
 template <int W>
 struct CountTotals {
@@ -547,6 +556,7 @@ __global__ __launch_bounds__(64 * W) void k_group_count_u8_files(
   const uint32_t f = blockIdx.x;
   const int64_t file_row0 = (int64_t)f * gm.rows;
   const uint32_t n_rounds = (gm.gpf + W - 1) / W;
+  const uint32_t fcap = gm.gpf * (uint32_t)kStageSlots;  // words of a file's region
   auto load_group = [&](uint32_t gi, u32x4 (&q)[kGroupRows]) -> int {  // gi: any value
     const int r0 = (int)gi * kGroupRows;
     const int nr = gi < gm.gpf ? min(kGroupRows, gm.rows - r0) : 0;
@@ -611,12 +621,13 @@ __global__ __launch_bounds__(64 * W) void k_group_count_u8_files(
     if (nr == 0) continue;  // wave-uniform; the barrier above is behind us
     const EmitSpan sp = emit_span(my_rank, total, es);
     const int64_t grp = (int64_t)f * gm.gpf + gi;
-    if (emit_staged(sp)) {  // wave-uniform
-      uint32_t* e = entries + grp * kStageSlots;
+    if (emit_staged_file(sp, fcap)) {  // wave-uniform
+      uint32_t* e = entries + (int64_t)f * fcap + sp.first;
+      const uint32_t row_bits = (gi * kGroupRows) << 18;  // rows <= 2^14 (staged_emitted)
       GroupLds& L = s_lds[w];
       group_to_lds(L, lane, m, incl, v);
       for (uint32_t j = (uint32_t)lane; j < sp.m; j += 64u)
-        e[j] = kept_entry(L, rb, sp.rank0 + j * es.stride);
+        e[j] = kept_entry(L, rb, sp.rank0 + j * es.stride) | row_bits;
       wave_lds_sync();  // the slice is rewritten by the next group
     }
     if (lane == 0) group_count[grp] = (int32_t)total;
@@ -635,13 +646,8 @@ __global__ __launch_bounds__(64 * W) void k_group_count_u8_files(
 //   3000           12 / 11.72          2498 .. 2596   2835 .. 2899
 //   6000           24 / 23.44                 4853         5510
 // So: the emitted layout when the busiest CU has at most 1/19 more than the average, from the
-// smallest stack it was measured ahead at.
-constexpr int64_t kCus = 256;  // MI355X
-constexpr int64_t kEmittedMinFiles = 1500;
-inline int64_t busiest_cu_files(int64_t n_files) { return (n_files + kCus - 1) / kCus; }
-inline bool staged_emitted(int64_t n_files) {
-  return n_files >= kEmittedMinFiles && n_files * 20 >= busiest_cu_files(n_files) * kCus * 19;
-}
+// smallest stack it was measured ahead at, for sweeps of at most 2^14 rows (the entry's row
+// field): staged_emitted(n_files, rows) in k1_emit.h, host arithmetic with its own host check.
 
 // Waves per file of the file-ordered count pass: the most of 4, 2, 1 with every workgroup
 // resident at once (a CU holds 32 waves and 160 KiB of LDS, a wave's GroupLds is 5 KiB: 7
@@ -733,8 +739,9 @@ __global__ __launch_bounds__(kBlock, 8) void k_group_write_u8(
     const int64_t out0 = file_offsets[f];
     const int32_t g = gain ? gain[f] : 0;
     const int32_t fr = (int32_t)(f / (uint32_t)files_per_frame);
-    const bool staged =
-        STAGED && (emitted ? emit_staged(sp) : total <= (uint32_t)kStageSlots);  // wave-uniform
+    const uint32_t fcap = gm.gpf * (uint32_t)kStageSlots;  // (emitted) words of a file's region
+    const bool staged = STAGED && (emitted ? emit_staged_file(sp, fcap)
+                                           : total <= (uint32_t)kStageSlots);  // wave-uniform
     uint32_t rb[kGroupRows + 1];
     if (!staged) {
       uint4 vv[kGroupRows];
@@ -757,7 +764,9 @@ __global__ __launch_bounds__(kBlock, 8) void k_group_write_u8(
         rb[k + 1] = rb[k] + (uint32_t)__builtin_amdgcn_readlane(incl[k], 63);
       group_to_lds(L, lane, m, incl, vv);
     }
-    const uint32_t* e = entries + (int64_t)grp * kStageSlots;
+    // the group's entries: its slot by rank; emitted, word `first` of its file's region
+    const uint32_t* e = entries + ((STAGED && emitted) ? (int64_t)f * fcap + first
+                                                       : (int64_t)grp * kStageSlots);
     for (uint32_t o = first + (uint32_t)lane; o < last; o += 64u) {
       const int64_t oo = out0 + o;
       if (oo >= cap) break;
@@ -765,7 +774,7 @@ __global__ __launch_bounds__(kBlock, 8) void k_group_write_u8(
       const uint32_t ent = !staged  ? kept_entry(L, rb, i)
                            : emitted ? e[o - first]
                                      : e[stage_pos(i, total, us == 4u)];
-      const int rk = (int)(ent >> 18);
+      const int rk = (int)((ent >> 18) & 3u);  // (emitted: the row within the file, mod 4)
       const float sc = rk == 0 ? r_sc[0] : (rk == 1 ? r_sc[1] : (rk == 2 ? r_sc[2] : r_sc[3]));
       const float cc = rk == 0 ? r_c[0] : (rk == 1 ? r_c[1] : (rk == 2 ? r_c[2] : r_c[3]));
       const float ss = rk == 0 ? r_s[0] : (rk == 1 ? r_s[1] : (rk == 2 ? r_s[2] : r_s[3]));
@@ -786,17 +795,15 @@ __global__ __launch_bounds__(kBlock, 8) void k_group_write_u8(
                    (int)(sizeof(GroupLds) / sizeof(uint32_t) / 4));
 }
 
-// ---- expand write: output slots to threads (staged groups)
+// ---- expand write: output slots to threads (staged groups), by-rank layout
 // The wave-per-group write above walks 3 M groups of ~16 outputs each with a dependent
 // prefix -> entry -> store chain per group; its time is that chain times the groups per wave
 // slot.  Here the outputs themselves are spread over the threads: per group one 64-bit word
 //   bits 0..39  gs    = global index of the group's first emitted output
-//   bits 40..62 phase = slot position of that output's entry: 0 in the emitted layout (output
-//               gs + d is entry d, for every stride); by rank its in-group kept rank
+//   bits 40..62 phase = slot position of that output's entry: its in-group kept rank
 //               (first * stride - rank < stride), or its residue's base at stride 4
-//   bit 63      the group emits outputs but is not staged (emitted layout: more than kStageSlots
-//               outputs, emit_staged; by rank: more than kStageSlots kept samples): they are
-//               written by k_group_write_u8<.., LIST> over the list of such groups
+//   bit 63      the group emits outputs but is not staged (more than kStageSlots kept samples):
+//               they are written by k_group_write_u8<.., LIST> over the list of such groups
 // and a block walks a contiguous range of 1024-output tiles, finding each output's group by a
 // binary search of an LDS window of those words (gs is non-decreasing in the group index).
 constexpr int kGsBits = 40;
@@ -810,7 +817,7 @@ constexpr int kWin = 1024;  // groups in the LDS window
 __global__ __launch_bounds__(kBlock) void k_group_starts(const int64_t* __restrict__ gprefix,
                                                         const int64_t* __restrict__ file_offsets,
                                                         uint32_t n_groups, uint32_t gpf,
-                                                        uint32_t stride, bool emitted,
+                                                        uint32_t stride,
                                                         uint64_t* __restrict__ gword,
                                                         uint32_t* __restrict__ list,
                                                         uint32_t* __restrict__ list_n) {
@@ -834,13 +841,11 @@ __global__ __launch_bounds__(kBlock) void k_group_starts(const int64_t* __restri
       const uint32_t total = (uint32_t)(gprefix[g + 1] - p0);
       const EmitSpan sp = emit_span(rank, total, es);
       const uint64_t gs = (uint64_t)file_offsets[f] + sp.first;
-      // slot position of the first emitted output's entry.  Emitted layout: 0.  By rank: its
-      // in-group rank, or with stride 4 (residues packed, stage_pos) the base of its residue
-      const uint64_t phase = emitted       ? 0ull
-                             : stride == 4u ? (uint64_t)phase_base(sp.rank0, total)
-                                            : (uint64_t)sp.rank0;
-      const bool un =
-          sp.m != 0u && !(emitted ? emit_staged(sp) : total <= (uint32_t)kStageSlots);
+      // slot position of the first emitted output's entry: its in-group rank, or with stride 4
+      // (residues packed, stage_pos) the base of its residue
+      const uint64_t phase = stride == 4u ? (uint64_t)phase_base(sp.rank0, total)
+                                          : (uint64_t)sp.rank0;
+      const bool un = sp.m != 0u && total > (uint32_t)kStageSlots;
       gword[g] = gs | (phase << kGsBits) | (un ? kUnstaged : 0ull);
       if (un) {
         const uint32_t slot = atomicAdd(&s_n, 1u);
@@ -978,8 +983,8 @@ __global__ __launch_bounds__(kBlock) void k_expand_write(
         ok[k] = in && !(w & kUnstaged);
         grp[k] = g;
         // the entry's slot position, mod 2^32 like the 64-bit form (only staged groups use it:
-        // idx < kStageSlots).  estep, the entries from one output to the next: 1 in the emitted
-        // layout and by rank at stride 4 (residues packed), else the stride
+        // idx < kStageSlots).  estep, the entries from one output to the next: 1 at stride 4
+        // (residues packed), else the stride
         const uint32_t d = (uint32_t)O - (uint32_t)w;
         idx[k] = d * estep + (uint32_t)((w & ~kUnstaged) >> kGsBits);
       }
@@ -1086,6 +1091,294 @@ __global__ __launch_bounds__(kBlock) void k_expand_write(
   if (bpart) xb.store_block(bpart, reinterpret_cast<uint32_t*>(s_win), 1);  // (window done)
 }
 
+// ---- streaming write: output slots to threads, file-contiguous layout
+// Output o of file f is word o of the file's region of C = gpf * kStageSlots words when
+// o < staged_out[f] (k1_emit.h emit_staged_out), and its global slot is file_offsets[f] + o: the
+// write pass is a stream over the regions with no group words and no per-output search.
+//
+// k_file_staged, one wave per file: staged_out[f], from the file's output count alone when it
+// is at most C (no group of the file is unstaged: file_offsets[f], [f + 1] and nothing else are
+// read).  Else the wave walks the file's group prefix, 64 groups at a time, and appends the
+// unstaged emitting groups to the list that k_group_write_u8<.., LIST> writes from the echo (one
+// global atomic per overflowing file: the groups are counted first and listed in a second walk).
+__global__ __launch_bounds__(kBlock) void k_file_staged(const int64_t* __restrict__ gprefix,
+                                                       const int64_t* __restrict__ file_offsets,
+                                                       uint32_t n_files, uint32_t gpf,
+                                                       uint32_t stride,
+                                                       uint32_t* __restrict__ staged_out,
+                                                       uint32_t* __restrict__ list,
+                                                       uint32_t* __restrict__ list_n) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t fcap = gpf * (uint32_t)kStageSlots;
+  for (uint32_t f = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + threadIdx.x / 64);
+       f < n_files; f += gridDim.x * kWavesPerBlock) {  // wave-uniform
+    // a file has fewer than 2^32 samples, so fewer outputs
+    const uint32_t count = (uint32_t)(file_offsets[f + 1] - file_offsets[f]);
+    uint32_t so = count;
+    if (count > fcap) {  // wave-uniform
+      const EmitStride es = emit_stride(stride);
+      const int64_t* gp = gprefix + (int64_t)f * gpf;
+      const int64_t p00 = gp[0];
+      auto unstaged = [&](uint32_t g, EmitSpan* sp) -> bool {
+        if (g >= gpf) return false;
+        const int64_t p0 = gp[g];
+        // in-file rank and kept count: a file has fewer than 2^32 samples
+        *sp = emit_span((uint32_t)(p0 - p00), (uint32_t)(gp[g + 1] - p0), es);
+        return emit_unstaged_file(*sp, fcap);
+      };
+      uint32_t n_un = 0u;
+      for (uint32_t g0 = 0u; g0 < gpf; g0 += 64u) {
+        EmitSpan sp{};
+        if (unstaged(g0 + lane, &sp)) {
+          so = emit_staged_out(so, sp, fcap);
+          ++n_un;
+        }
+      }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) {
+        so = min(so, (uint32_t)__shfl_xor((int)so, off));
+        n_un += (uint32_t)__shfl_xor((int)n_un, off);
+      }
+      uint32_t base = 0u;
+      if (lane == 0u) base = atomicAdd(list_n, n_un);
+      base = __builtin_amdgcn_readfirstlane(base);
+      for (uint32_t g0 = 0u; g0 < gpf; g0 += 64u) {
+        EmitSpan sp{};
+        const bool un = unstaged(g0 + lane, &sp);
+        const uint64_t b = __ballot(un);
+        if (un) list[base + (uint32_t)rank_in_mask(b)] = f * gpf + g0 + lane;
+        base += (uint32_t)__popcll(b);
+      }
+    }
+    if (lane == 0u) staged_out[f] = so;
+  }
+}
+
+constexpr int kFWin = kBlock;  // file offsets in the LDS window: one per thread
+
+// largest i in [lo, hi) with fo[i] <= O, given fo[lo] <= O: one wave, 64-ary search
+__device__ uint32_t wave_find_file(const int64_t* __restrict__ fo, uint32_t lo, uint32_t hi,
+                                   int64_t O) {
+  const uint32_t lane = threadIdx.x & 63u;
+  while (hi - lo > 1u) {
+    const uint32_t step = (hi - lo + 63u) / 64u;
+    const uint32_t idx = lo + lane * step;
+    const bool le = idx < hi && fo[idx] <= O;  // a prefix of the lanes
+    const uint64_t m = __ballot(le);
+    const uint32_t top = 63u - (uint32_t)__clzll((long long)m);
+    lo = __builtin_amdgcn_readfirstlane(lo + top * step);
+    hi = min(hi, lo + step);
+  }
+  return lo;
+}
+
+// same, one thread (the rare outputs beyond the LDS window)
+__device__ uint32_t thread_find_file(const int64_t* __restrict__ fo, uint32_t lo, uint32_t hi,
+                                     int64_t O) {
+  while (hi - lo > 1u) {
+    const uint32_t mid = lo + (hi - lo) / 2u;
+    if (fo[mid] <= O)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+
+// largest j < wn with s_fo[j] <= O (s_fo[0] <= O)
+__device__ __forceinline__ uint32_t lds_find_file(const int64_t* s_fo, uint32_t wn, int64_t O) {
+  uint32_t lo = 0u;
+#pragma unroll
+  for (uint32_t step = kFWin / 2; step > 0u; step >>= 1)
+    if (lo + step < wn && s_fo[lo + step] <= O) lo += step;
+  return lo;
+}
+
+// k_expand_stream: a block walks a contiguous range of 1024-output tiles, 4 consecutive outputs
+// per thread.  A thread finds the file of its first output by a binary search of an LDS window of
+// file_offsets (n_files + 1 values, the last one the total, so an output below the total always
+// has a file) and steps over file boundaries and empty files for the other three.
+// VEC, VT, cap, bpart: as k_expand_write's.
+template <bool VEC, class VT = float>
+__global__ __launch_bounds__(kBlock) void k_expand_stream(
+    const int64_t* __restrict__ file_offsets, uint32_t n_files,
+    const uint32_t* __restrict__ staged_out, GroupMap gm, const float* __restrict__ scale,
+    const float* __restrict__ cos_t, const float* __restrict__ sin_t,
+    const int32_t* __restrict__ gain, int files_per_frame, float* __restrict__ x,
+    float* __restrict__ y, VT* __restrict__ val, int32_t* __restrict__ gain_out,
+    int32_t* __restrict__ pf_out, int64_t cap, const uint32_t* __restrict__ entries,
+    uint32_t* __restrict__ bpart = nullptr) {
+  __shared__ int64_t s_fo[kFWin];
+  __shared__ uint32_t s_flo;
+  const uint32_t n_off = n_files + 1u;  // values of file_offsets
+  const int64_t total = min(file_offsets[n_files], cap);
+  const int64_t n_tiles = (total + kTileOut - 1) / kTileOut;
+  const int64_t t0 = n_tiles * blockIdx.x / gridDim.x;
+  const int64_t t1 = n_tiles * (blockIdx.x + 1) / gridDim.x;
+  if (t0 >= t1) {  // block-uniform
+    if (bpart && threadIdx.x < 4)  // (no outputs: the identity)
+      bpart[4 * blockIdx.x + threadIdx.x] = (threadIdx.x & 1) ? 0u : 0xffffffffu;
+    return;
+  }
+  if (threadIdx.x < 64) {
+    const uint32_t f = wave_find_file(file_offsets, 0u, n_off, t0 * kTileOut);
+    if (threadIdx.x == 0) s_flo = f;
+  }
+  __syncthreads();
+  // the window of the next tile is loaded into a register while this tile's entries, geometry
+  // and stores are in flight
+  int64_t wv;
+  auto load_win = [&](uint32_t flo_) {
+    wv = threadIdx.x < min((uint32_t)kFWin, n_off - flo_) ? file_offsets[flo_ + threadIdx.x]
+                                                          : INT64_MAX;
+  };
+  uint32_t flo = s_flo;
+  XyBounds xb;
+  load_win(flo);
+  s_fo[threadIdx.x] = wv;
+  __syncthreads();
+  const uint32_t fcap = gm.gpf * (uint32_t)kStageSlots;  // words of a file's region
+  const uint32_t fpf = (uint32_t)files_per_frame;
+  const float inv_bins = 1.0f / 1024.0f;  // exact: step = scale / 1024 == scale * 2^-10
+  for (int64_t t = t0; t < t1; ++t) {
+    const uint32_t wn = min((uint32_t)kFWin, n_off - flo);
+    const bool truncated = flo + wn < n_off;
+    const int64_t O0 = t * kTileOut;
+    auto off = [&](uint32_t i) -> int64_t {  // file_offsets[i], i <= n_files
+      return (i - flo < wn) ? s_fo[i - flo] : file_offsets[i];
+    };
+    // phase A: the file and the in-file index of this thread's kOutPerThread consecutive outputs
+    const int64_t Ob = O0 + (int64_t)threadIdx.x * kOutPerThread;
+    uint32_t fl[kOutPerThread], oi[kOutPerThread];
+    bool in[kOutPerThread];
+    if (Ob < total) {
+      const uint32_t j = lds_find_file(s_fo, wn, Ob);
+      uint32_t f = (j == wn - 1u && truncated) ? thread_find_file(file_offsets, flo + j, n_off, Ob)
+                                               : flo + j;
+      int64_t base = off(f), nx = off(f + 1u);
+#pragma unroll
+      for (int k = 0; k < kOutPerThread; ++k) {
+        const int64_t O = Ob + k;
+        in[k] = O < total;
+        while (in[k] && O >= nx) {  // (O < total = the last offset: f stays below n_files)
+          ++f;
+          base = nx;
+          nx = off(f + 1u);
+        }
+        fl[k] = f;
+        oi[k] = (uint32_t)(O - base);
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < kOutPerThread; ++k) {
+        in[k] = false;
+        fl[k] = flo;
+        oi[k] = 0u;
+      }
+    }
+    // the next tile's first file (thread 0), before the window is rewritten
+    if (threadIdx.x == 0 && t + 1 < t1) {
+      const int64_t On = O0 + kTileOut;
+      const uint32_t j = lds_find_file(s_fo, wn, On);
+      s_flo = (j == wn - 1u && truncated) ? thread_find_file(file_offsets, flo + j, n_off, On)
+                                          : flo + j;
+    }
+    __syncthreads();  // every search of this window done; s_flo of the next tile visible
+    if (t + 1 < t1) {
+      flo = s_flo;
+      load_win(flo);
+    }
+    // phase B: the staged entries and the files' staged counts, then the rows' geometry, then
+    // the stores.  Every load unconditional and masked by selects (conditional loads would each
+    // end in a full vmcnt wait): an output that is not written reads word 0 and, when it is
+    // beyond the file's staged outputs but inside its region, a word that may never have been
+    // written; either is dropped before its row field is used.
+    uint32_t ent[kOutPerThread];
+    bool ok[kOutPerThread];
+#pragma unroll
+    for (int k = 0; k < kOutPerThread; ++k) {
+      const uint32_t so = staged_out[fl[k]];  // <= fcap
+      const uint32_t e =
+          entries[(in[k] && oi[k] < fcap) ? (int64_t)fl[k] * fcap + oi[k] : (int64_t)0];
+      ok[k] = in[k] && oi[k] < so;
+      ent[k] = ok[k] ? e : 0u;
+    }
+    float sc[kOutPerThread], cc[kOutPerThread], ss[kOutPerThread];
+    uint32_t pfl[kOutPerThread];
+    // one division per thread: its outputs' files are fl[0] or a few after it (steps over frame
+    // boundaries; a long run of empty files divides again)
+    uint32_t pf = fl[0] / fpf, q = fl[0] - pf * fpf;
+#pragma unroll
+    for (int k = 0; k < kOutPerThread; ++k) {
+      if (k > 0) {
+        q += fl[k] - fl[k - 1];
+        if (q >= fpf) {
+          if (q < 2u * fpf) {
+            q -= fpf;
+            ++pf;
+          } else {
+            const uint32_t d = q / fpf;
+            pf += d;
+            q -= d * fpf;
+          }
+        }
+      }
+      pfl[k] = pf;
+      const int64_t row = (int64_t)fl[k] * gm.rows + (ent[k] >> 18);
+      sc[k] = scale[row];
+      cc[k] = cos_t[row];
+      ss[k] = sin_t[row];
+    }
+    float ox[kOutPerThread], oy[kOutPerThread];
+    int32_t og[kOutPerThread], op[kOutPerThread];
+    bool all_ok = true;
+#pragma unroll
+    for (int k = 0; k < kOutPerThread; ++k) {
+      const float rr = sc[k] * inv_bins * (float)((ent[k] >> 8) & 1023u);
+      ox[k] = rr * cc[k];
+      oy[k] = rr * ss[k];
+      og[k] = gain ? gain[fl[k]] : 0;
+      op[k] = (int32_t)pfl[k];
+      all_ok = all_ok && ok[k];
+      if (bpart && ok[k]) xb.add(ox[k], oy[k]);
+    }
+    if (VEC && all_ok) {  // 16-B stores (the common case)
+#pragma unroll
+      for (int h = 0; h < kOutPerThread; h += 4) {
+        const int64_t o = Ob + h;
+        *reinterpret_cast<float4*>(x + o) = make_float4(ox[h], ox[h + 1], ox[h + 2], ox[h + 3]);
+        *reinterpret_cast<float4*>(y + o) = make_float4(oy[h], oy[h + 1], oy[h + 2], oy[h + 3]);
+        if constexpr (sizeof(VT) == 1)
+          *reinterpret_cast<uint32_t*>(val + o) =
+              (ent[h] & 0xffu) | ((ent[h + 1] & 0xffu) << 8) | ((ent[h + 2] & 0xffu) << 16) |
+              ((ent[h + 3] & 0xffu) << 24);
+        else
+          *reinterpret_cast<float4*>(val + o) =
+              make_float4((float)(ent[h] & 0xffu), (float)(ent[h + 1] & 0xffu),
+                          (float)(ent[h + 2] & 0xffu), (float)(ent[h + 3] & 0xffu));
+        if (gain_out)
+          *reinterpret_cast<int4*>(gain_out + o) = make_int4(og[h], og[h + 1], og[h + 2], og[h + 3]);
+        if (pf_out)
+          *reinterpret_cast<int4*>(pf_out + o) = make_int4(op[h], op[h + 1], op[h + 2], op[h + 3]);
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < kOutPerThread; ++k) {
+        if (!ok[k]) continue;
+        const int64_t oo = Ob + k;
+        x[oo] = ox[k];
+        y[oo] = oy[k];
+        val[oo] = (VT)(ent[k] & 0xffu);
+        if (gain_out) gain_out[oo] = og[k];
+        if (pf_out) pf_out[oo] = op[k];
+      }
+    }
+    if (t + 1 < t1) s_fo[threadIdx.x] = wv;
+    __syncthreads();  // the next tile's window
+  }
+  if (bpart) xb.store_block(bpart, reinterpret_cast<uint32_t*>(s_fo), 1);  // (window done)
+}
+
 // integer threshold of u8 samples (see keep_bits)
 inline int u8_threshold(float thr) {
   if (!(thr == thr)) return 255;
@@ -1110,8 +1403,8 @@ inline uint32_t u8_k(int T) {
   return (uint32_t)(T <= 127 ? 127 - T : 255 - T) * 0x01010101u;
 }
 
-// k_expand_write: a persistent grid (8 blocks per CU of the 256; each walks a contiguous tile
-// range).  ab().k1_expand off keeps the wave-per-group write for A/B runs.
+// k_expand_write and k_expand_stream: a persistent grid (8 blocks per CU of the 256; each walks a
+// contiguous tile range).  ab().k1_expand off keeps the wave-per-group write for A/B runs.
 constexpr int kExpandBlocks = 2048;
 constexpr int kListBlocks = 2048;  // blocks of the unstaged groups' write (at most)
 
@@ -1151,7 +1444,7 @@ int32_t count_impl(const T* echo, int64_t n_files, int rows, int bins, float thr
     RPT_K1F(false, W);    \
   else                    \
     RPT_K1F(true, W)
-    if (entries && staged_emitted(n_files)) {
+    if (entries && staged_emitted(n_files, rows)) {
       switch (count_waves_per_file(n_files)) {
         case 4: RPT_K1FW(4); break;
         case 2: RPT_K1FW(2); break;
@@ -1218,37 +1511,59 @@ int32_t write_impl(const T* echo, int64_t n_files, int rows, int bins, float thr
     const int grid = grid_for(n_groups, kWavesPerBlock, 16384);
     const int T8 = u8_threshold(thr);
     const auto* e8 = reinterpret_cast<const uint8_t*>(echo);
-    const bool emitted = staged_emitted(n_files);  // the entries' layout, as the count pass
-    if (entries && ab().k1_expand && stride < (1 << 23) &&
-        n_files * (int64_t)rows * 1024 < (int64_t(1) << kGsBits)) {
-      // staged entries: outputs to threads (k_expand_write); the few unstaged groups listed by
-      // k_group_starts are written by the wave-per-group kernel
+    const bool emitted = staged_emitted(n_files, rows);  // the entries' layout, as the count pass
+    if (entries && ab().k1_expand &&
+        (emitted || (stride < (1 << 23) &&
+                     n_files * (int64_t)rows * 1024 < (int64_t(1) << kGsBits)))) {
+      // staged entries: outputs to threads.  File-contiguous: k_file_staged + k_expand_stream;
+      // by rank: k_group_starts + k_expand_write.  The few unstaged groups that the first kernel
+      // of either pair lists are written by the wave-per-group kernel
       Scratch& sc = scratch(st);
       Budget b;
-      b.add<uint64_t>(n_groups);
+      if (emitted)
+        b.add<uint32_t>(n_files);
+      else
+        b.add<uint64_t>(n_groups);
       b.add<uint32_t>(n_groups);
       RPT_TRY(sc.reserve(b.bytes, st));
-      uint64_t* gword = sc.carve_n<uint64_t>(n_groups);
+      uint64_t* gword = emitted ? nullptr : sc.carve_n<uint64_t>(n_groups);
+      uint32_t* staged_out = emitted ? sc.carve_n<uint32_t>(n_files) : nullptr;
       uint32_t* list = sc.carve_n<uint32_t>(n_groups);
       uint32_t* list_n = nullptr;
       RPT_TRY(zero_n(st, 1, &list_n));
-      hipLaunchKernelGGL(k_group_starts, dim3(grid_for(n_groups, kBlock, 4096)), dim3(kBlock), 0,
-                         st, row_prefix, file_offsets, (uint32_t)n_groups, gm.gpf,
-                         (uint32_t)stride, emitted, gword, list, list_n);
+      if (emitted)
+        hipLaunchKernelGGL(k_file_staged, dim3(grid_for(n_files, kWavesPerBlock)), dim3(kBlock), 0,
+                           st, row_prefix, file_offsets, (uint32_t)n_files, gm.gpf,
+                           (uint32_t)stride, staged_out, list, list_n);
+      else
+        hipLaunchKernelGGL(k_group_starts, dim3(grid_for(n_groups, kBlock, 4096)), dim3(kBlock), 0,
+                           st, row_prefix, file_offsets, (uint32_t)n_groups, gm.gpf,
+                           (uint32_t)stride, gword, list, list_n);
       RPT_CHECK_LAUNCH();
       auto al16 = [](const void* q) { return ((uintptr_t)q & 15u) == 0; };
       const bool vec4 = al16(x) && al16(y) && al16(v) && (!gout || al16(gout)) && (!pf || al16(pf));
-      const uint32_t estep = (emitted || stride == 4) ? 1u : (uint32_t)stride;
-      if (vec4)
-        hipLaunchKernelGGL((k_expand_write<true, VT>), dim3(kExpandBlocks), dim3(kBlock), 0, st, gword,
-                           (uint32_t)n_groups, gm, estep, geo.scale, geo.cos_t, geo.sin_t, gain,
-                           file_offsets + n_files, fpf, x, y, v, gout, pf, cap, entries,
-                           bnd ? bnd + 4 : nullptr);
-      else
-        hipLaunchKernelGGL((k_expand_write<false, VT>), dim3(kExpandBlocks), dim3(kBlock), 0, st,
-                           gword, (uint32_t)n_groups, gm, estep, geo.scale, geo.cos_t, geo.sin_t,
-                           gain, file_offsets + n_files, fpf, x, y, v, gout, pf, cap, entries,
-                           bnd ? bnd + 4 : nullptr);
+      const uint32_t estep = stride == 4 ? 1u : (uint32_t)stride;
+      uint32_t* bpart = bnd ? bnd + 4 : nullptr;
+#define RPT_K1S(VEC)                                                                             \
+  hipLaunchKernelGGL((k_expand_stream<VEC, VT>), dim3(kExpandBlocks), dim3(kBlock), 0, st,        \
+                     file_offsets, (uint32_t)n_files, staged_out, gm, geo.scale, geo.cos_t,      \
+                     geo.sin_t, gain, fpf, x, y, v, gout, pf, cap, entries, bpart)
+#define RPT_K1E(VEC)                                                                             \
+  hipLaunchKernelGGL((k_expand_write<VEC, VT>), dim3(kExpandBlocks), dim3(kBlock), 0, st, gword,  \
+                     (uint32_t)n_groups, gm, estep, geo.scale, geo.cos_t, geo.sin_t, gain,       \
+                     file_offsets + n_files, fpf, x, y, v, gout, pf, cap, entries, bpart)
+      if (emitted) {
+        if (vec4)
+          RPT_K1S(true);
+        else
+          RPT_K1S(false);
+      } else if (vec4) {
+        RPT_K1E(true);
+      } else {
+        RPT_K1E(false);
+      }
+#undef RPT_K1E
+#undef RPT_K1S
       RPT_CHECK_LAUNCH();
       const int lgrid = std::min(grid, kListBlocks);
 #define RPT_K1L(HI)                                                                            \
