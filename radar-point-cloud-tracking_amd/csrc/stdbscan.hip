@@ -15,22 +15,47 @@
 //   border    =    non-core point with a core neighbour: minimum adjacent cluster id
 //   noise     =    -1
 //
-// Pipeline (K4..K8 of SURVEY.md §8a):
-//   k_bounds      min/max per dimension and time, "times integral" flag        (1 sync)
-//   k_keys        cell key per point: ((slab*nz + cz)*ny + cy)*nx + cx
-//   radix sort    stable, so every cell lists its points in index order
-//   k_gather      sorted float4 {x, y, z|t, t} + original index (the slab writers: float2 {x, y}
-//                 where no kernel of the run needs a point's time, DbscanState::xy_points)
-//   k_cell_count  -> exclusive scan -> cell_start[C+1]
-//   k_cell_box    per occupied cell: bounding box in space and time, "mutual" flag
-//                 (box diagonal within eps and time span within eps_t: every pair adjacent)
-//   k_core        neighbour count with early exit at min_samples; whole-cell accept/reject
-//   k_cell_min_pair  the minimum-original-index core point of each cell (star init)
-//   k_union       core-core union-find (min-index hooking); one edge per mutual cell suffices
-//   k_compress    root of every point
-//   k_cmin        minimum original index per component
-//   k_ismin/scan  cluster id = rank of the component minimum among all minima
-//   k_label       core: own id; non-core: min id over adjacent core points, else -1
+// Pipeline (K4..K8 of SURVEY.md §8a).  This file is the one translation unit: the DbscanState
+// kernels of K4 to K6 with the helpers every stage reads, the DbscanState driver, the fused
+// entry points and the phased C-ABI bodies.  The label and denoise kernels are in stage files
+// included (inside namespace rpt { namespace {) after the K6 kernels they read:
+//   this file            K4, DbscanState::build_t:
+//       k_bounds, k_bounds_final   min/max per dimension and time, "times integral" flag (1 sync)
+//       time-ordered finite 2-D points, a slab's cells within LDS: a counting sort per slab
+//         k_slab_lo, then k_slab_bucket (one block per slab), or in chunks k_slab_chunk_hist,
+//         k_slab_chunk_scan (or k_chunk_totals, k_chunk_cursors, k_occ_write, k_cell_start_end,
+//         k_slab_occ_base around two scans) and k_slab_chunk_scatter; a scan and k_occ_gather
+//         (the writers: sorted float4 {x, y, t, t}, or float2 {x, y} where no kernel of the run
+//         needs a point's time, DbscanState::xy_points)
+//       otherwise k_keys (cell key per point: ((slab*nz + cz)*ny + cy)*nx + cx), a stable radix
+//         sort, k_gather (sorted float4 {x, y, z|t, t} + original index), k_cell_runs, scans ->
+//         cell_start[C+1], k_occ_list
+//       k_cell_box / k_cell_box_mixed   per occupied cell: point range, bounding box in space and
+//         time, "mutual" flag (box diagonal within eps and time span within eps_t: every pair
+//         adjacent); k_slab_range: the time range per slab
+//   this file            K5, DbscanState::core_pass: neighbour count with early exit at
+//       min_samples; whole-cell accept/reject
+//       2-D, at most kCwMaxR slabs each side: k_core_cells_oct, then k_core_slow_masked (or
+//         k_core_slow) over the queued points
+//       otherwise k_core_cell_fast, k_core_cell_window, k_core_fill, k_core_slow
+//   this file            K6, DbscanState::union_pass: core-core union-find (min-index hooking);
+//       one edge per mutual cell suffices
+//       k_init_occ_cells, k_cell_min_pair (the minimum-original-index core point of each cell),
+//       k_parent_init_cells or k_parent_init_pair (star init)
+//       2-D: k_union_cells_pair, k_cell_root_snapshot, k_union_listed, k_union_nm
+//       3-D: k_union_cells<3, false>, k_union_cells<3, true>, k_union<3>
+//   stdbscan_label.inc   K7/K8, DbscanState::cluster_ids, labels_local, labels_global and the
+//       phased bodies: cluster id = rank of the component minimum among all minima (MinRank);
+//       core: own id; non-core: min id over adjacent core points, else -1
+//       local, per-cell path (cell_comp): k_cell_comp, k_word_popc, scan, k_label_core_cells
+//       local, otherwise: k_cell_roots, k_ccmin, k_word_popc, scan, k_label_core(_orig)
+//       then k_label over the queued non-core points
+//       global: k_cell_roots, k_ccmin_global, k_label_global_orig, k_label_global_core, k_label
+//       phased: k_core_to_orig, k_core_from_orig, k_comp_out, k_comp_out_edges
+//   stdbscan_frames.inc  denoise variant, DbscanState::frames_pass and labels_fifo:
+//       k_frames_cells, k_frames_queue, k_frames_points / k_frames_points_list; k_inverse_perm,
+//       k_label_core_orig, k_label_fifo
+//   stdbscan_ab.inc      the replaced forms, A/B build only (RPT_AB; included by the label file)
 //
 // Cell side is 0.7 eps in 2-D and eps/2 in 3-D (x (1+2^-20)): at least eps/2, so every neighbour
 // lies within +-2 cells, and small enough that a full cell's diagonal (0.99 eps in 2-D,
@@ -43,6 +68,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -3249,1078 +3275,8 @@ __global__ __launch_bounds__(kBlock) void k_union_nm(const float4* __restrict__ 
   }
 }
 
-__global__ __launch_bounds__(kBlock) void k_fill_i32(int32_t* p, int64_t n, int32_t v) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    p[i] = v;
-}
-
-// Cluster id of a component minimum m = its rank among the minima: one bit per original index
-// (set by k_ccmin) and an exclusive scan of the words' popcounts (total = cluster count at
-// pref[words]): n/32 words to clear and scan instead of an n-length flag array.
-struct MinRank {
-  const uint32_t* bits;
-  const int32_t* pref;
-  __device__ __forceinline__ int32_t operator[](int32_t m) const {
-    const uint32_t w = bits[m >> 5];
-    return pref[m >> 5] + __popc(w & ((1u << (m & 31)) - 1u));
-  }
-};
-
-__global__ void k_word_popc(const uint32_t* __restrict__ bits, int64_t words,
-                            int32_t* __restrict__ out) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < words;
-       i += (int64_t)gridDim.x * blockDim.x)
-    out[i] = __popc(bits[i]);
-}
-
-// ccmin[s] = component-min original index for core points, -1 otherwise; flags the minima and
-// queues the non-core points for k_label.
-// Root of every occupied mutual cell's core points (its representative's root): the core points
-// of a mutual cell all hang under the representative (star init), so k_ccmin takes their root
-// from here -- one cached per-cell read instead of a parent chain per point.
-__global__ __launch_bounds__(kBlock) void k_cell_roots(int32_t* parent,
-                                                      const int32_t* __restrict__ occ,
-                                                      const int32_t* __restrict__ n_occ,
-                                                      int64_t cells,
-                                                      const uint8_t* __restrict__ mutual,
-                                                      const int32_t* __restrict__ rep,
-                                                      int32_t* __restrict__ cell_root,
-                                                      int32_t* __restrict__ zero = nullptr,
-                                                      uint32_t* __restrict__ zwords = nullptr,
-                                                      int64_t nzw = 0,
-                                                      int32_t* __restrict__ cmin_fill = nullptr) {
-  // zero (nullable): a counter of the next kernel, cleared here instead of by a memset launch;
-  // likewise the label pass's minimum bits (zwords, nzw words) and its per-cell smallest keys
-  // (cmin_fill: every cell INT_MAX) -- both first written by k_ccmin / k_ccmin_global next
-  if (zero && blockIdx.x == 0 && threadIdx.x == 0) *zero = 0;
-  {
-    const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t ts = (int64_t)gridDim.x * blockDim.x;
-    if (zwords)
-      for (int64_t i = t0; i < nzw; i += ts) zwords[i] = 0u;
-    if (cmin_fill)
-      for (int64_t i = t0; i < cells; i += ts) cmin_fill[i] = INT_MAX;
-  }
-  const int64_t m = *n_occ;
-  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < m;
-       q += (int64_t)gridDim.x * blockDim.x) {
-    const int32_t c = occ[q];
-    if ((int64_t)c >= cells) continue;
-    const int r = mutual[c] ? rep[c] : -1;
-    cell_root[c] = (r >= 0) ? uf_find(parent, r) : -1;  // -1: walk each point's own chain
-  }
-}
-
-// cell_root (nullable): k_cell_roots' output (-1: not a mutual cell with core points), read for
-// core points through skey.
-// cell_key (nullable, pre-filled with INT_MAX): per cell the smallest component key among its
-// core points, by a segmented wave minimum over the sorted points (k_cell_min_key fused in).
-// The kItems points of a thread go through the dependent loads level by level (keys + flags,
-// cell roots, component minima), each level's loads in flight together; the atomics come last.
-__global__ __launch_bounds__(kBlock) void k_ccmin(int32_t* parent,
-                                                 const uint8_t* __restrict__ core, int64_t n,
-                                                 const int32_t* __restrict__ sorig,
-                                                 int32_t* __restrict__ ccmin,
-                                                 uint32_t* __restrict__ min_bits,
-                                                 int32_t* __restrict__ nc_list,
-                                                 int32_t* __restrict__ nc_count,
-                                                 const int32_t* __restrict__ skey = nullptr,
-                                                 const uint8_t* __restrict__ mutual = nullptr,
-                                                 const int32_t* __restrict__ cell_root = nullptr,
-                                                 int64_t cells = 0,
-                                                 int32_t* __restrict__ cell_key = nullptr) {
-  const int lane = threadIdx.x & 63;
-  (void)mutual;
-  for (int64_t tile = (int64_t)blockIdx.x * kBlock * kItems; tile < n;
-       tile += (int64_t)gridDim.x * kBlock * kItems) {
-    int32_t key[kItems], x[kItems];
-    uint32_t cbits = 0, inb = 0;
-#pragma unroll
-    // levels 1, 2 and 4 load branch-free (clamped indices, results masked), so each level's
-    // loads are in flight together; only the parent-chain walk (points outside mutual cells)
-    // stays conditional
-    for (int k = 0; k < kItems; ++k) {
-      const int64_t s = tile + (int64_t)k * kBlock + threadIdx.x;
-      const int64_t sc = min(s, n - 1);
-      const int32_t kv = skey ? skey[sc] : -1;  // kernel-uniform pointer test
-      const uint8_t cv = core[sc];
-      const bool in = s < n;
-      key[k] = in ? kv : -1;
-      inb |= in ? (1u << k) : 0u;
-      cbits |= (in && cv) ? (1u << k) : 0u;
-    }
-#pragma unroll
-    for (int k = 0; k < kItems; ++k) {
-      x[k] = -1;
-      if (cell_root) {  // kernel-uniform
-        const bool q = ((cbits >> k) & 1u) && key[k] >= 0 && (int64_t)key[k] < cells;
-        const int32_t r = cell_root[q ? key[k] : 0];  // cells >= 1
-        x[k] = q ? r : -1;
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < kItems; ++k) {
-      const int s = (int)(tile + (int64_t)k * kBlock + threadIdx.x);
-      if (((cbits >> k) & 1u) && x[k] < 0) x[k] = uf_find(parent, s);
-    }
-    int m[kItems];
-#pragma unroll
-    for (int k = 0; k < kItems; ++k) {
-      const bool c = (cbits >> k) & 1u;
-      const int32_t v = sorig[c ? x[k] : 0];
-      m[k] = c ? v : -1;
-    }
-#pragma unroll
-    for (int k = 0; k < kItems; ++k) {
-      const int64_t s = tile + (int64_t)k * kBlock + threadIdx.x;
-      if ((inb >> k) & 1u) ccmin[s] = m[k];
-      if (((cbits >> k) & 1u) && x[k] == (int)s) atomicOr(min_bits + (m[k] >> 5), 1u << (m[k] & 31));
-    }
-    if (cell_key) {  // kernel-uniform: every lane of the wave takes part
-#pragma unroll
-      for (int k = 0; k < kItems; ++k) {
-        int v = (m[k] >= 0 && (int64_t)key[k] < cells) ? m[k] : INT_MAX;
-        const int kk = key[k];
-        // sorted keys: a run of equal keys is one cell; dist = lanes since this lane's run head
-        const int prevk = __shfl_up(kk, 1, 64), next = __shfl_down(kk, 1, 64);
-        const uint64_t hm = __ballot(lane == 0 || prevk != kk);
-        const uint64_t upto = (lane == 63) ? ~0ull : ((2ull << lane) - 1ull);
-        const int dist = lane - (63 - __builtin_clzll(hm & upto));
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-          const int ov = __shfl_up(v, off, 64);
-          if (off <= dist) v = min(v, ov);
-        }
-        if ((lane == 63 || next != kk) && kk >= 0 && v != INT_MAX) atomicMin(cell_key + kk, v);
-      }
-    }
-    block_append_bits(tile, inb & ~cbits, nc_list, nc_count);
-  }
-}
-
-// queue of the non-core points (phased / global labelling)
-__global__ __launch_bounds__(kBlock) void k_nc_list(const uint8_t* __restrict__ core, int64_t n,
-                                                   int32_t* __restrict__ nc_list,
-                                                   int32_t* __restrict__ nc_count) {
-  for (int64_t tile = (int64_t)blockIdx.x * kBlock * kItems; tile < n;
-       tile += (int64_t)gridDim.x * kBlock * kItems)
-    block_append(
-        tile, n, [&](int64_t s) -> bool { return !core[s]; }, nc_list, nc_count);
-}
-
-// K7/K8 (core points): label = id of the component minimum
-__global__ __launch_bounds__(kBlock) void k_label_core(const int32_t* __restrict__ ccmin,
-                                                      int64_t n,
-                                                      const int32_t* __restrict__ sorig,
-                                                      MinRank cid,
-                                                      int32_t* __restrict__ labels) {
-  // kPU points per thread per tile, loads branch-free (clamped, masked): two memory rounds per
-  // tile (ccmin + sorig, then the rank words) instead of two per point.  XCD-contiguous tiles
-  // (grid a multiple of 8): the blocks of one XCD take one eighth of the sorted points, i.e. a
-  // run of whole frames, so the labels they scatter (original order, within those frames) fill
-  // their lines in that XCD's L2 instead of eight L2s writing partial lines of the same frames
-  const int64_t T = (n + (int64_t)kBlock * kPU - 1) / ((int64_t)kBlock * kPU);
-  const bool xm = (gridDim.x & 7) == 0;
-  const int64_t xg = blockIdx.x & 7, nbx = gridDim.x >> 3;
-  const int64_t t_lo = xm ? T * xg / 8 : blockIdx.x, t_hi = xm ? T * (xg + 1) / 8 : T;
-  const int64_t t_step = xm ? nbx : gridDim.x;
-  for (int64_t ti = t_lo + (xm ? (int64_t)(blockIdx.x >> 3) : 0); ti < t_hi; ti += t_step) {
-    const int64_t tile = ti * kBlock * kPU;
-    int32_t own[kPU], so[kPU];
-#pragma unroll
-    for (int u = 0; u < kPU; ++u) {
-      const int64_t s = min(tile + (int64_t)u * kBlock + threadIdx.x, n - 1);
-      own[u] = ccmin[s];
-      so[u] = sorig[s];
-    }
-    uint32_t w[kPU];
-    int32_t pr[kPU];
-#pragma unroll
-    for (int u = 0; u < kPU; ++u) {
-      const int32_t m = own[u] >= 0 ? own[u] : 0;
-      w[u] = cid.bits[m >> 5];
-      pr[u] = cid.pref[m >> 5];
-    }
-#pragma unroll
-    for (int u = 0; u < kPU; ++u) {
-      const int64_t s = tile + (int64_t)u * kBlock + threadIdx.x;
-      if (s < n && own[u] >= 0)
-        labels[so[u]] = pr[u] + __popc(w[u] & ((1u << (own[u] & 31)) - 1u));
-    }
-  }
-}
-
-// The same in ORIGINAL order through the grid build's inverse permutation spos: the labels are
-// written in whole lines and the component keys gathered (a frame's keys stay in L2) instead of
-// 4-byte label writes scattered over each frame, whose partly written lines L2 evicts (dense
-// share: 1.23 GB written for 0.25 GB of labels).  Non-core points are left to k_label.
-__global__ __launch_bounds__(kBlock) void k_label_core_orig(const int32_t* __restrict__ ccmin,
-                                                           int64_t n,
-                                                           const int32_t* __restrict__ spos,
-                                                           MinRank cid,
-                                                           int32_t* __restrict__ labels) {
-  const int64_t T = (n + (int64_t)kBlock * kPU - 1) / ((int64_t)kBlock * kPU);
-  const bool xm = (gridDim.x & 7) == 0;  // XCD-contiguous tiles (runs of whole frames)
-  const int64_t xg = blockIdx.x & 7, nbx = gridDim.x >> 3;
-  const int64_t t_lo = xm ? T * xg / 8 : blockIdx.x, t_hi = xm ? T * (xg + 1) / 8 : T;
-  const int64_t t_step = xm ? nbx : gridDim.x;
-  for (int64_t ti = t_lo + (xm ? (int64_t)(blockIdx.x >> 3) : 0); ti < t_hi; ti += t_step) {
-    const int64_t tile = ti * kBlock * kPU;
-    int32_t sp[kPU], own[kPU];
-#pragma unroll
-    for (int u = 0; u < kPU; ++u)  // branch-free (clamped); streamed once
-      sp[u] = __builtin_nontemporal_load(spos + min(tile + (int64_t)u * kBlock + threadIdx.x,
-                                                     n - 1));
-#pragma unroll
-    for (int u = 0; u < kPU; ++u) own[u] = ccmin[sp[u]];
-    uint32_t w[kPU];
-    int32_t pr[kPU];
-#pragma unroll
-    for (int u = 0; u < kPU; ++u) {
-      const int32_t m = own[u] >= 0 ? own[u] : 0;
-      w[u] = cid.bits[m >> 5];
-      pr[u] = cid.pref[m >> 5];
-    }
-#pragma unroll
-    for (int u = 0; u < kPU; ++u) {
-      const int64_t i = tile + (int64_t)u * kBlock + threadIdx.x;
-      if (i < n && own[u] >= 0)
-        labels[i] = pr[u] + __popc(w[u] & ((1u << (own[u] & 31)) - 1u));
-    }
-  }
-}
-
-// ---- component ids per CELL (all_mutual grids; after k_parent_init_cells and the union passes)
-// Every occupied cell is mutual, so its core points share one component and the component
-// minimum is a per-cell value: cell_key[c] = sorig[root(rep[c])] (cells without core points keep
-// k_parent_init_cells' INT_MAX).  The cell whose representative is the root flags the minimum's
-// bit.  Replaces k_cell_roots + k_ccmin: one thread per occupied cell instead of per point, and
-// no per-point ccmin[] at all (k_label_core_cells reads cell_key through skey).
-// zero: the non-core queue counter of k_label_core_cells (the union passes' list counter until
-// here).
-__global__ __launch_bounds__(kBlock) void k_cell_comp(int32_t* parent,
-                                                     const int32_t* __restrict__ occ,
-                                                     const int32_t* __restrict__ n_occ,
-                                                     int64_t cells,
-                                                     const int32_t* __restrict__ rep,
-                                                     const int32_t* __restrict__ sorig,
-                                                     int32_t* __restrict__ cell_key,
-                                                     uint32_t* __restrict__ min_bits,
-                                                     int32_t* __restrict__ zero) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) *zero = 0;
-  const int64_t m = *n_occ;
-  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < m;
-       q += (int64_t)gridDim.x * blockDim.x) {
-    const int32_t c = occ[q];
-    if ((int64_t)c >= cells) continue;
-    const int r = rep[c];
-    if (r < 0) continue;
-    const int root = uf_find(parent, r);
-    const int32_t k = sorig[root];
-    cell_key[c] = k;
-    if (root == r) atomicOr(min_bits + (k >> 5), 1u << (k & 31));
-  }
-}
-
-// K7/K8 (core points) on all_mutual grids, with the non-core queue folded in: a core point's
-// label is the rank of its CELL's component minimum (cell_key[skey[s]]; sorted points are runs of
-// equal keys, so the lookup is a broadcast load), a non-core point is queued for k_label.
-// ORIG = false: over the sorted points, labels scattered through sorig (as k_label_core);
-// ORIG = true : over the original indices through the inverse permutation spos (as
-//               k_label_core_orig), the key and flag gathered, the queue entry = spos[i].
-// kPU points per thread per tile, loads branch-free level by level, XCD-contiguous tiles (see
-// k_label_core).
-// guard: the box-certain union pass's count of non-mutual cells with core points.  all_mutual
-// promises zero; if it is not, the labels are not valid and the cluster count (written by the
-// scan before this kernel) is replaced by -1, which fails the call at the readback of the count.
-struct AppendSpos {
-  const int32_t* spos;
-  __device__ int32_t operator()(int64_t i) const { return spos[i]; }
-};
-template <bool ORIG>
-__global__ __launch_bounds__(kBlock) void k_label_core_cells(
-    const int32_t* __restrict__ skey, const uint8_t* __restrict__ core,
-    const int32_t* __restrict__ perm, int64_t n, int64_t cells,
-    const int32_t* __restrict__ cell_key, MinRank cid, int32_t* __restrict__ labels,
-    int32_t* __restrict__ nc_list, int32_t* __restrict__ nc_count,
-    const int32_t* __restrict__ guard, int32_t* __restrict__ n_clusters) {
-  if (blockIdx.x == 0 && threadIdx.x == 0 && *guard != 0) *n_clusters = -1;
-  const int64_t T = (n + (int64_t)kBlock * kPU - 1) / ((int64_t)kBlock * kPU);
-  const bool xm = (gridDim.x & 7) == 0;
-  const int64_t xg = blockIdx.x & 7, nbx = gridDim.x >> 3;
-  const int64_t t_lo = xm ? T * xg / 8 : blockIdx.x, t_hi = xm ? T * (xg + 1) / 8 : T;
-  const int64_t t_step = xm ? nbx : gridDim.x;
-  for (int64_t ti = t_lo + (xm ? (int64_t)(blockIdx.x >> 3) : 0); ti < t_hi; ti += t_step) {
-    const int64_t tile = ti * kBlock * kPU;
-    int32_t pv[kPU], k[kPU];
-    uint32_t c[kPU];
-    if (ORIG) {
-#pragma unroll
-      for (int u = 0; u < kPU; ++u)  // streamed once
-        pv[u] = __builtin_nontemporal_load(perm + min(tile + (int64_t)u * kBlock + threadIdx.x,
-                                                       n - 1));
-#pragma unroll
-      for (int u = 0; u < kPU; ++u) {
-        k[u] = skey[pv[u]];
-        c[u] = core[pv[u]];
-      }
-    } else {
-#pragma unroll
-      for (int u = 0; u < kPU; ++u) {
-        const int64_t s = min(tile + (int64_t)u * kBlock + threadIdx.x, n - 1);
-        k[u] = skey[s];
-        c[u] = core[s];
-        pv[u] = perm[s];
-      }
-    }
-    int32_t own[kPU];
-    uint32_t inb = 0, cb = 0;
-#pragma unroll
-    for (int u = 0; u < kPU; ++u) {
-      const bool in = tile + (int64_t)u * kBlock + threadIdx.x < n;
-      const bool q = in && c[u] != 0u && k[u] >= 0 && (int64_t)k[u] < cells;
-      inb |= in ? (1u << u) : 0u;
-      cb |= (in && c[u] != 0u) ? (1u << u) : 0u;
-      const int32_t v = cell_key[q ? k[u] : 0];  // cells >= 1
-      own[u] = (q && v != INT_MAX) ? v : -1;
-    }
-    uint32_t w[kPU];
-    int32_t pr[kPU];
-#pragma unroll
-    for (int u = 0; u < kPU; ++u) {
-      const int32_t m = own[u] >= 0 ? own[u] : 0;
-      w[u] = cid.bits[m >> 5];
-      pr[u] = cid.pref[m >> 5];
-    }
-#pragma unroll
-    for (int u = 0; u < kPU; ++u) {
-      if (own[u] >= 0) {
-        const int32_t lab = pr[u] + __popc(w[u] & ((1u << (own[u] & 31)) - 1u));
-        if (ORIG)
-          labels[tile + (int64_t)u * kBlock + threadIdx.x] = lab;
-        else
-          labels[pv[u]] = lab;
-      }
-    }
-    if (ORIG)
-      block_append_bits(tile, inb & ~cb, nc_list, nc_count, AppendSpos{perm});
-    else
-      block_append_bits(tile, inb & ~cb, nc_list, nc_count);
-  }
-}
-
-// K7/K8 (non-core points, queued): the smallest component key over adjacent core points, else
-// none.  One wave per point, one lane per candidate cell of its window.  A cell whose box is
-// wholly adjacent contributes its smallest key (cell_key) with no point read; the others are
-// resolved in increasing cell_key order and only while that key can still beat the best so far:
-// a mutual cell (one component) needs one adjacent core point, any other cell the smallest key
-// among its adjacent core points.
-// GLOBAL = false: key = ccmin (component-min original index, local run), label = cid[key];
-// GLOBAL = true : key = slab (the core point's final label: labels are ranks of the sorted global
-//                 representatives, so the smallest label is the smallest representative).
-// ALLMUT (all_mutual grids, local run): every candidate cell with core points is mutual and key_of
-//                 (ccmin) is not written -- the core flag core_of[j] stands for key_of[j] >= 0, the
-//                 non-mutual search and the mutual[] loads compile out.
-// XY: float2 points (ALLMUT grids only); the window comes from the key's slab.
-template <int D, bool GLOBAL, int W = 64, bool ALLMUT = false, bool XY = false>
-// 6 waves/SIMD (80 VGPRs, no spill; with two candidate points per lane per round 7 spilled 8)
-// W = 32: two points per wave, one per half (the same candidate loads per point, twice the
-// points in flight: the pass is a chain of dependent loads per point, not bandwidth)
-__global__ __launch_bounds__(kBlock, 6) void k_label(const Pt<XY>* __restrict__ pts,
-                                                 const int32_t* __restrict__ skey, Geom g,
-                                                 const CellRec<D>* __restrict__ crec,
-                                                 const uint32_t* __restrict__ occ_bits,
-                                                 const float2* __restrict__ slab_t,
-                                                 const int32_t* __restrict__ key_of,
-                                                 const int32_t* __restrict__ cell_key,
-                                                 const uint8_t* __restrict__ mutual,
-                                                 const int32_t* __restrict__ sorig,
-                                                 MinRank cid,
-                                                 const int32_t* __restrict__ nc_list,
-                                                 const int32_t* __restrict__ nc_count,
-                                                 int32_t* __restrict__ labels,
-                                                 int32_t* __restrict__ kstat = nullptr,
-                                                 const uint8_t* __restrict__ core_of = nullptr) {
-  static_assert(!ALLMUT || (D == 2 && !GLOBAL), "all-mutual grids are 2-D, local runs");
-  static_assert(!XY || ALLMUT, "xy points only on all-mutual grids");
-  // kstat (A/B build, RPT_STATS): queued points, points with a core cell in their window, points
-  // that searched a partly reachable cell, points labelled
-  static_assert(W == 32 || W == 64, "a point per wave or per half-wave");
-  constexpr int P = 64 / W;  // points per wave
-  const int lane = threadIdx.x & 63;
-  const int hl = lane & (W - 1);      // lane within the point's group
-  const int h0 = lane - hl;           // the group's first lane
-  const int shift = (W == 64) ? 0 : h0;
-  // the group's bits of a wave ballot
-  auto gbal = [&](bool v) -> uint64_t {
-    const uint64_t b = __ballot(v);
-    return (W == 64) ? b : ((b >> shift) & 0xffffffffull);
-  };
-  auto gmin = [&](int v) -> int {  // rows by DPP, then the 16 (and 32) lane steps
-    v = row_reduce<16>(v, OpMin{});
-    v = min(v, __shfl_xor(v, 16));
-    if (W == 64) v = min(v, __shfl_xor(v, 32));
-    return v;
-  };
-  const int64_t nc = *nc_count;
-  // XCD-aware ranges of the (cell-ordered) queue: neighbouring points' windows share an L2
-  const XcdRange xr = xcd_items((nc + P - 1) / P, true);
-  for (int64_t qp = xr.first; qp < xr.end; qp += xr.step) {
-    const int64_t q = qp * P + (lane / W);
-    if (q >= nc) continue;  // (group-uniform)
-    const int s = nc_list[q];
-    const int32_t key = skey[s];
-    int best = INT_MAX;
-#ifdef RPT_AB
-    bool st_core = false, st_search = false;
-#endif
-    if ((int64_t)key < g.cells) {
-      const float4 p = load_pt<XY>(pts, s);
-      int cx, cy, cz;
-      decode_key<D>(key, g, cx, cy, cz);
-      const Window w = XY ? slab_window<D>(cx, cy, cz, g.slab_of_key(key), g)
-                          : make_window<D, false>(cx, cy, cz, p.w, p.w, g, slab_t);
-      // super-rounds of kR candidates per lane, loads of one kind issued together: the cells'
-      // smallest keys (empty cells hold INT_MAX, so no occupancy lookup), then the records of
-      // the cells with core points -- two dependent rounds per super-round
-      for (int base = 0; base < w.total; base += W * kR) {
-        int64_t c[kR];
-        int ck[kR], cb[kR], ce[kR], cls[kR], mu[kR];
-#pragma unroll
-        for (int k = 0; k < kR; ++k) {
-          const int qq = base + k * W + hl;
-          c[k] = (qq < w.total) ? window_cell<D>(w, qq, g, slab_t, p.w, p.w) : -1;
-        }
-#pragma unroll
-        for (int k = 0; k < kR; ++k) ck[k] = (c[k] >= 0) ? cell_key[c[k]] : INT_MAX;
-        int v = INT_MAX;
-#pragma unroll
-        for (int k = 0; k < kR; ++k) {
-          cb[k] = ce[k] = cls[k] = mu[k] = 0;
-          if (ck[k] != INT_MAX) {
-            const CellRec<D> cr = crec[c[k]];
-            cb[k] = cr.b;
-            ce[k] = cr.e;
-            mu[k] = ALLMUT ? 1 : mutual[c[k]];
-            cls[k] = classify<D, XY>(p, rec_boxA<D>(cr), rec_boxB(cr), g);
-            if (cls[k] == 1) v = min(v, ck[k]);
-          }
-        }
-        best = min(best, gmin(v));
-#ifdef RPT_AB
-        {
-          bool anyc = false;
-#pragma unroll
-          for (int k = 0; k < kR; ++k) anyc = anyc || ck[k] != INT_MAX;
-          st_core = st_core || gbal(anyc) != 0;
-        }
-#endif
-        // the partially reachable cells, smallest key first, while a key can still win
-        uint32_t pend = 0;
-#pragma unroll
-        for (int k = 0; k < kR; ++k) pend |= (cls[k] == 2) ? (1u << k) : 0u;
-        while (true) {
-          int mine = INT_MAX, mk = -1;
-#pragma unroll
-          for (int k = 0; k < kR; ++k)
-            if (((pend >> k) & 1u) && ck[k] < best && ck[k] < mine) {
-              mine = ck[k];
-              mk = k;
-            }
-          const int mm = gmin(mine);
-          if (mm == INT_MAX) break;
-#ifdef RPT_AB
-          st_search = true;
-#endif
-          const uint64_t at = gbal(mine == mm);
-          const int l = h0 + __ffsll((unsigned long long)at) - 1;
-          const int kl = __shfl(mk, l);
-          int bsel = 0, esel = 0, msel = 0;
-#pragma unroll
-          for (int k = 0; k < kR; ++k)
-            if (k == kl) {
-              bsel = cb[k];
-              esel = ce[k];
-              msel = mu[k];
-            }
-          if (lane == l) pend &= ~(1u << kl);
-          const int bl = __shfl(bsel, l), el = __shfl(esel, l);
-          // two points per lane per round (their loads issued together): a dense cell costs
-          // half the dependent round trips
-          if (ALLMUT || __shfl(msel, l)) {  // one component: a single adjacent core point decides
-            bool hit = false;
-            for (int j0 = bl; j0 < el && !hit; j0 += 2 * W) {
-              const int j = j0 + hl, j2 = j + W;
-              const bool v1 = j < el, v2 = j2 < el;
-              int k1, k2;
-              if (ALLMUT) {
-                k1 = (v1 && core_of[j]) ? 0 : -1;
-                k2 = (v2 && core_of[j2]) ? 0 : -1;
-              } else {
-                k1 = v1 ? key_of[j] : -1;
-                k2 = v2 ? key_of[j2] : -1;
-              }
-              const float4 p1 = v1 ? load_pt<XY>(pts, j) : p;
-              const float4 p2 = v2 ? load_pt<XY>(pts, j2) : p;
-              hit = gbal((k1 >= 0 && adjacent<D, XY>(p, p1, g)) ||
-                         (k2 >= 0 && adjacent<D, XY>(p, p2, g))) != 0;
-            }
-            if (hit) best = mm;
-          } else {
-            int lb = INT_MAX;
-            for (int j0 = bl; j0 < el; j0 += 2 * W) {
-              const int j = j0 + hl, j2 = j + W;
-              const bool v1 = j < el, v2 = j2 < el;
-              const int m1 = v1 ? key_of[j] : -1, m2 = v2 ? key_of[j2] : -1;
-              const float4 p1 = v1 ? load_pt<XY>(pts, j) : p;
-              const float4 p2 = v2 ? load_pt<XY>(pts, j2) : p;
-              if (m1 >= 0 && m1 < best && m1 < lb && adjacent<D, XY>(p, p1, g)) lb = m1;
-              if (m2 >= 0 && m2 < best && m2 < lb && adjacent<D, XY>(p, p2, g)) lb = m2;
-            }
-            best = min(best, gmin(lb));
-          }
-        }
-      }
-    }
-    if (hl == 0) {
-      int32_t out = -1;
-      if (best != INT_MAX) out = GLOBAL ? best : cid[best];
-      labels[sorig[s]] = out;
-#ifdef RPT_AB
-      if (kstat) {
-        atomicAdd(&kstat[0], 1);
-        if (st_core) atomicAdd(&kstat[1], 1);
-        if (st_search) atomicAdd(&kstat[2], 1);
-        if (best != INT_MAX) atomicAdd(&kstat[3], 1);
-      }
-#endif
-    }
-  }
-}
-
-#ifdef RPT_AB
-#include "stdbscan_ab.inc"
-#endif
-
-// Degenerate parameters (negative/NaN eps): nobody has a neighbour, not even itself.
-__global__ __launch_bounds__(kBlock) void k_isolated_labels(int32_t* labels, int64_t n,
-                                                           int singletons) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    labels[i] = singletons ? (int32_t)i : -1;
-}
-
-// Non-finite-time points are isolated; with min_samples <= 0 they are singleton clusters and
-// flagged as their own component minimum (handled by k_ccmin via parent = self).
-
-// ---------------------------------------------------------------- phased state (multi-GPU)
-__global__ void k_core_to_orig(const uint8_t* __restrict__ core, const int32_t* __restrict__ sorig,
-                               int64_t n, uint8_t* __restrict__ out) {
-  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n;
-       s += (int64_t)gridDim.x * blockDim.x)
-    out[sorig[s]] = core[s];
-}
-__global__ void k_core_from_orig(const uint8_t* __restrict__ in, const int32_t* __restrict__ sorig,
-                                 int64_t n, uint8_t* __restrict__ core) {
-  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n;
-       s += (int64_t)gridDim.x * blockDim.x)
-    core[s] = in[sorig[s]] ? 1 : 0;
-}
-// comp[orig] = minimum original index of the point's core component, -1 for non-core; a core
-// point of a mutual cell takes its cell's root (k_cell_roots: one load instead of a parent-chain
-// walk per point)
-__global__ void k_comp_out(int32_t* parent, const uint8_t* __restrict__ core,
-                           const int32_t* __restrict__ sorig, int64_t n,
-                           int32_t* __restrict__ comp, const int32_t* __restrict__ skey,
-                           const int32_t* __restrict__ cell_root, int64_t cells) {
-  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n;
-       s += (int64_t)gridDim.x * blockDim.x) {
-    int32_t out = -1;
-    if (core[s]) {
-      const int32_t key = skey[s];
-      const int32_t cr = ((int64_t)key < cells) ? cell_root[key] : -1;  // -1: not mutual
-      out = sorig[cr >= 0 ? cr : uf_find(parent, (int)s)];
-    }
-    comp[sorig[s]] = out;
-  }
-}
-// k_comp_out for the original indices outside [lo_end, hi_begin) only (the frame-sharded
-// driver needs the component ids of its halo points and of its own edge points, not of the
-// window's interior): every sorted point is read (one coalesced index load), only the edge
-// points pay a root lookup and a scattered store
-__global__ void k_comp_out_edges(int32_t* parent, const uint8_t* __restrict__ core,
-                                 const int32_t* __restrict__ sorig, int64_t n,
-                                 int32_t* __restrict__ comp, const int32_t* __restrict__ skey,
-                                 const int32_t* __restrict__ cell_root, int64_t cells,
-                                 int64_t lo_end, int64_t hi_begin) {
-  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n;
-       s += (int64_t)gridDim.x * blockDim.x) {
-    const int32_t i = sorig[s];
-    if (i >= lo_end && i < hi_begin) continue;
-    int32_t out = -1;
-    if (core[s]) {
-      const int32_t key = skey[s];
-      const int32_t cr = (cell_root && (int64_t)key < cells) ? cell_root[key] : -1;
-      out = sorig[cr >= 0 ? cr : uf_find(parent, (int)s)];
-    }
-    comp[i] = out;
-  }
-}
-// Global labelling, core points: ccmin[s] = component-min original index; each component's
-// label = rank of its global representative (rep[min], from the equivalence merge) among the
-// sorted representatives -- one binary search per component, at its root; non-core queued.
-__global__ __launch_bounds__(kBlock) void k_ccmin_global(int32_t* parent,
-                                                        const uint8_t* __restrict__ core,
-                                                        int64_t n,
-                                                        const int32_t* __restrict__ sorig,
-                                                        const int64_t* __restrict__ rep,
-                                                        const int64_t* __restrict__ reps,
-                                                        int64_t nr, int32_t* __restrict__ ccmin,
-                                                        int32_t* __restrict__ gl,
-                                                        int32_t* __restrict__ nc_list,
-                                                        int32_t* __restrict__ nc_count,
-                                                        const int32_t* __restrict__ skey = nullptr,
-                                                        const uint8_t* __restrict__ mutual = nullptr,
-                                                        const int32_t* __restrict__ cell_root = nullptr,
-                                                        int64_t cells = 0,
-                                                        const int64_t* __restrict__ nr_dev = nullptr) {
-  if (nr_dev) nr = *nr_dev;  // the representative count stays on the device (shard driver)
-  // level by level as in k_ccmin (keys + flags, cell roots, originals: branch-free loads, each
-  // level's loads in flight together); only the parent-chain walk stays conditional
-  for (int64_t tile = (int64_t)blockIdx.x * kBlock * kItems; tile < n;
-       tile += (int64_t)gridDim.x * kBlock * kItems) {
-    int32_t key[kItems], x[kItems];
-    uint32_t cbits = 0, nbits = 0;
-#pragma unroll
-    for (int k = 0; k < kItems; ++k) {
-      const int64_t s = tile + (int64_t)k * kBlock + threadIdx.x;
-      const int64_t sc = min(s, n - 1);
-      const int32_t kv = cell_root ? skey[sc] : -1;  // kernel-uniform pointer test
-      const uint8_t cv = core[sc];
-      const bool in = s < n;
-      key[k] = in ? kv : -1;
-      cbits |= (in && cv) ? (1u << k) : 0u;
-      nbits |= (in && !cv) ? (1u << k) : 0u;  // non-core: queued for k_label
-    }
-#pragma unroll
-    for (int k = 0; k < kItems; ++k) {
-      x[k] = -1;
-      if (cell_root) {  // core points of a mutual cell: their cell's root (k_cell_roots)
-        const bool q = ((cbits >> k) & 1u) && key[k] >= 0 && (int64_t)key[k] < cells;
-        const int32_t kk = q ? key[k] : 0;  // cells >= 1
-        const uint8_t mu = mutual[kk];
-        const int32_t cr = cell_root[kk];
-        x[k] = (q && mu) ? cr : -1;
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < kItems; ++k) {
-      const int s = (int)(tile + (int64_t)k * kBlock + threadIdx.x);
-      if (((cbits >> k) & 1u) && x[k] < 0) x[k] = uf_find(parent, s);
-    }
-    int m[kItems];
-#pragma unroll
-    for (int k = 0; k < kItems; ++k) {
-      const bool c = (cbits >> k) & 1u;
-      const int32_t v = sorig[c ? x[k] : 0];
-      m[k] = c ? v : -1;
-    }
-#pragma unroll
-    for (int k = 0; k < kItems; ++k) {
-      const int64_t s = tile + (int64_t)k * kBlock + threadIdx.x;
-      if ((cbits >> k) & 1u) {
-        ccmin[s] = m[k];
-        if (x[k] == (int)s) gl[m[k]] = rep_id(reps, nr, rep[m[k]]);
-      }
-    }
-    block_append_bits(tile, nbits, nc_list, nc_count);
-  }
-}
-// The core labels in original order through the grid build's inverse permutation (spos, the
-// slab buffer before k_label_global_core reuses it): whole-line label writes (k_label_core_orig)
-__global__ __launch_bounds__(kBlock) void k_label_global_orig(const uint8_t* __restrict__ core,
-                                                             const int32_t* __restrict__ ccmin,
-                                                             const int32_t* __restrict__ gl,
-                                                             const int32_t* __restrict__ spos,
-                                                             int64_t n,
-                                                             int32_t* __restrict__ labels) {
-  const int64_t T = (n + (int64_t)kBlock * kPU - 1) / ((int64_t)kBlock * kPU);
-  for (int64_t ti = blockIdx.x; ti < T; ti += gridDim.x) {
-    const int64_t tile = ti * kBlock * kPU;
-    int32_t sp[kPU], m[kPU];
-    uint8_t c[kPU];
-#pragma unroll
-    for (int u = 0; u < kPU; ++u)  // branch-free (clamped)
-      sp[u] = __builtin_nontemporal_load(spos + min(tile + (int64_t)u * kBlock + threadIdx.x,
-                                                     n - 1));
-#pragma unroll
-    for (int u = 0; u < kPU; ++u) {
-      c[u] = core[sp[u]];
-      m[u] = ccmin[sp[u]];
-    }
-#pragma unroll
-    for (int u = 0; u < kPU; ++u) {
-      const int64_t i = tile + (int64_t)u * kBlock + threadIdx.x;
-      if (i < n && c[u]) labels[i] = gl[m[u]];
-    }
-  }
-}
-
-// slab[s] = final label of core point s (-1 for non-core); core labels written out
-// The core points' final labels (slab[s] = label, -1 for non-core) and, k_cell_min_key folded in,
-// per cell the smallest label of its core points (cell_key pre-filled with INT_MAX): a segmented
-// wave minimum over the sorted points, one atomic per cell run of a wave.
-__global__ __launch_bounds__(kBlock) void k_label_global_core(const uint8_t* __restrict__ core,
-                                                             const int32_t* __restrict__ ccmin,
-                                                             const int32_t* __restrict__ gl,
-                                                             const int32_t* __restrict__ sorig,
-                                                             int64_t n,
-                                                             int32_t* __restrict__ slab,
-                                                             int32_t* __restrict__ labels,
-                                                             const int32_t* __restrict__ skey,
-                                                             int64_t cells,
-                                                             int32_t* __restrict__ cell_key) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t s0 = (int64_t)blockIdx.x * blockDim.x; s0 < n;
-       s0 += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t s = s0 + threadIdx.x;
-    int32_t l = -1, key = -1;
-    if (s < n) {
-      key = skey[s];
-      if (core[s]) {
-        l = gl[ccmin[s]];
-        if (labels) labels[sorig[s]] = l;  // (kernel-uniform; null: k_label_global_orig's)
-      }
-      slab[s] = l;
-    }
-    int v = (l >= 0 && (int64_t)key < cells) ? l : INT_MAX;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int ov = __shfl_up(v, off, 64);
-      const int ok = __shfl_up(key, off, 64);
-      if (lane >= off && ok == key) v = min(v, ov);
-    }
-    const int next = __shfl_down(key, 1, 64);
-    if ((lane == 63 || next != key) && key >= 0 && v != INT_MAX) atomicMin(cell_key + key, v);
-  }
-}
-
-// ---------------------------------------------------------------- denoise variant (O8)
-// PointCloudWorkF/stdbscan_denoising_pipeline.py:264-369.  A point is core when it has
-// >= min_samples space-time neighbours (itself included, as K5) AND those neighbours span
-// >= min_frames distinct int32(t) frames (:308-315); clusters are expanded with a FIFO queue that
-// never re-queues a visited point (:346-363).  The component structure is K6's; only the core
-// condition and the border rule differ (see k_label_fifo).
-//
-// Frames, cell level (every finite t integral: a slab is one frame): a cell whose column (same
-// x, y) holds, in >= min_frames - 1 other slabs, a cell every point of which is a neighbour of
-// every point of this cell (box test) has all its core points frame-complete.
-__global__ __launch_bounds__(kBlock) void k_frames_cells(Geom g, int R,
-                                                        const int32_t* __restrict__ occ,
-                                                        const int32_t* __restrict__ n_occ,
-                                                        const CellRec<2>* __restrict__ crec,
-                                                        const uint32_t* __restrict__ occ_bits,
-                                                        int min_frames,
-                                                        uint8_t* __restrict__ fok) {
-  const int64_t no = *n_occ;
-  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < no;
-       q += (int64_t)gridDim.x * blockDim.x) {
-    const int32_t ca = occ[q];
-    if ((int64_t)ca >= g.cells) continue;  // non-finite time: settled per point
-    int cx, cy, cz_, cs;
-    g.split((uint32_t)ca, cx, cy, cz_, cs);
-    const CellRec<2> ra = crec[ca];
-    const float4 A1 = rec_boxA<2>(ra), B1 = rec_boxB(ra);
-    int frames = 1;  // the cell's own
-    const int s0 = max(cs - R, 0), s1 = min(cs + R, g.nt - 1);
-    for (int sl = s0; sl <= s1 && frames < min_frames; ++sl) {
-      if (sl == cs) continue;
-      const int64_t c = ((int64_t)sl * g.ny + cy) * g.nx + cx;
-      if (!((occ_bits[c >> 5] >> (c & 31)) & 1u)) continue;
-      const CellRec<2> rc = crec[c];
-      // (box A of both cells, then box B of both: classify_cells' argument order)
-      frames += (classify_cells<2>(A1, rec_boxA<2>(rc), B1, rec_boxB(rc), g) == 1) ? 1 : 0;
-    }
-    fok[ca] = frames >= min_frames ? 1 : 0;
-  }
-}
-
-// Queue of the core points whose frame count is still open; points of the isolated cell
-// (non-finite t: no neighbour, 0 frames) are settled here.
-__global__ __launch_bounds__(kBlock) void k_frames_queue(const int32_t* __restrict__ skey,
-                                                        int64_t n, int64_t cells,
-                                                        const uint8_t* __restrict__ fok,
-                                                        int min_frames, int refine,
-                                                        uint8_t* __restrict__ core,
-                                                        int32_t* __restrict__ list,
-                                                        int32_t* __restrict__ count) {
-  for (int64_t tile = (int64_t)blockIdx.x * kBlock * kItems; tile < n;
-       tile += (int64_t)gridDim.x * kBlock * kItems)
-    block_append(
-        tile, n,
-        [&](int64_t s) -> bool {
-          if (!core[s]) return false;
-          const int32_t key = skey[s];
-          if ((int64_t)key >= cells) {
-            core[s] = (min_frames <= 0) ? 1 : 0;
-            return false;
-          }
-          return refine && !(fok && fok[key]);
-        },
-        list, count);
-}
-
-// Frame count of one queued core point per wave: the int32(t) offsets (within +-31 of its own:
-// |dt| <= eps_t <= 30, checked by the host) of its neighbours as a 64-bit set, scanned cell by
-// cell until min_frames distinct frames are seen.
-template <int D>
-__global__ __launch_bounds__(kBlock) void k_frames_points(const float4* __restrict__ pts,
-                                                         const int32_t* __restrict__ skey, Geom g,
-                                                         const CellRec<D>* __restrict__ crec,
-                                                         const uint32_t* __restrict__ occ_bits,
-                                                         const float2* __restrict__ slab_t,
-                                                         int integral, int min_frames,
-                                                         const int32_t* __restrict__ list,
-                                                         const int32_t* __restrict__ count,
-                                                         uint8_t* __restrict__ core) {
-  const int lane = threadIdx.x & 63;
-  const int64_t w0 = (int64_t)blockIdx.x * (kBlock / 64) + threadIdx.x / 64;
-  const int64_t nw = (int64_t)gridDim.x * (kBlock / 64);
-  const int64_t nq = *count;
-  for (int64_t q = w0; q < nq; q += nw) {
-    const int s = list[q];
-    const float4 p = pts[s];
-    const int own = (int)p.w;  // numpy astype(int32): truncation toward zero
-    int cx, cy, cz;
-    decode_key<D>(skey[s], g, cx, cy, cz);
-    const Window w = make_window<D, false>(cx, cy, cz, p.w, p.w, g, slab_t);
-    uint64_t seen = 0;
-    for (int base = 0; base < w.total && __popcll(seen) < min_frames; base += 64) {
-      const int qq = base + lane;
-      const int64_t c = (qq < w.total) ? window_cell<D>(w, qq, g, slab_t, p.w, p.w) : -1;
-      int b = 0, e = 0, cls = 0;
-      if (c >= 0 && ((occ_bits[c >> 5] >> (c & 31)) & 1u)) {
-        const CellRec<D> cr = crec[c];
-        b = cr.b;
-        e = cr.e;
-        cls = classify<D>(p, rec_boxA<D>(cr), rec_boxB(cr), g);
-      }
-      uint64_t pm = __ballot(cls != 0);
-      while (pm && __popcll(seen) < min_frames) {
-        const int l = __ffsll((unsigned long long)pm) - 1;
-        pm &= pm - 1;
-        const int bb = __shfl(b, l), cl = __shfl(cls, l);
-        // a whole-cell hit in frame-id data is one frame: its first point says which
-        const int ee = (cl == 1 && integral) ? bb + 1 : __shfl(e, l);
-        for (int j0 = bb; j0 < ee && __popcll(seen) < min_frames; j0 += 64) {
-          const int j = j0 + lane;
-          uint64_t bit = 0;
-          if (j < ee) {
-            const float4 pj = pts[j];
-            if (cl == 1 || adjacent<D>(p, pj, g))  // |t| >= 2^31 (saturating casts): clamped
-              bit = 1ull << min(max((int)pj.w - own + 32, 0), 63);
-          }
-#pragma unroll
-          for (int off = 32; off > 0; off >>= 1)
-            bit |= (uint64_t)__shfl_xor((unsigned long long)bit, off);
-          seen |= bit;
-        }
-      }
-    }
-    if (lane == 0) core[s] = (__popcll(seen) >= min_frames) ? 1 : 0;
-  }
-}
-
-// numpy float32 -> int32 astype on x86-64: truncation; NaN / out of range -> INT32_MIN
-__device__ __forceinline__ int32_t np_i32(float v) {
-  if (!(v == v) || v >= 2147483648.f || v < -2147483648.f) return INT32_MIN;
-  return (int32_t)v;
-}
-
-// The same frame count for any eps_t (k_frames_points' 64-bit offset set needs |dt| <= 30): the
-// distinct int32(t) frames seen so far are a list spread over the wave, kFramesPerLane per lane
-// (lane k holds entries k, k + 64, ...), appended one new frame at a time, so at most
-// min_frames <= 64 * kFramesPerLane entries ever exist (the host checks the bound).
-constexpr int kFramesPerLane = 4;
-template <int D>
-__global__ __launch_bounds__(kBlock) void k_frames_points_list(
-    const float4* __restrict__ pts, const int32_t* __restrict__ skey, Geom g,
-    const CellRec<D>* __restrict__ crec, const uint32_t* __restrict__ occ_bits,
-    const float2* __restrict__ slab_t, int integral, int min_frames,
-    const int32_t* __restrict__ list, const int32_t* __restrict__ count,
-    uint8_t* __restrict__ core) {
-  const int lane = threadIdx.x & 63;
-  const int64_t w0 = (int64_t)blockIdx.x * (kBlock / 64) + threadIdx.x / 64;
-  const int64_t nw = (int64_t)gridDim.x * (kBlock / 64);
-  const int64_t nq = *count;
-  for (int64_t q = w0; q < nq; q += nw) {
-    const int s = list[q];
-    const float4 p = pts[s];
-    int cx, cy, cz;
-    decode_key<D>(skey[s], g, cx, cy, cz);
-    const Window w = make_window<D, false>(cx, cy, cz, p.w, p.w, g, slab_t);
-    int32_t fr[kFramesPerLane];
-#pragma unroll
-    for (int k = 0; k < kFramesPerLane; ++k) fr[k] = 0;
-    int nseen = 0;
-    // v (this lane's candidate frame, valid when has): add it unless already listed
-    auto add = [&](bool has, int32_t v) {
-      bool fresh = has;
-      // membership: compare against every listed entry (broadcast one register row at a time;
-      // nseen is wave-uniform, so every lane runs every shuffle)
-#pragma unroll
-      for (int r = 0; r < kFramesPerLane; ++r) {
-        if (r * 64 >= nseen) break;
-        const int lim = min(nseen - r * 64, 64);
-        for (int k = 0; k < lim; ++k) {
-          const int32_t e = __shfl(fr[r], k);
-          if (e == v) fresh = false;
-        }
-      }
-      // append the distinct fresh values, lowest lane first
-      uint64_t m = __ballot(fresh);
-      while (m && nseen < min_frames) {
-        const int l = __ffsll((unsigned long long)m) - 1;
-        const int32_t nv = __shfl(v, l);
-        const int r = nseen / 64, k = nseen % 64;
-#pragma unroll
-        for (int rr = 0; rr < kFramesPerLane; ++rr)
-          if (rr == r && lane == k) fr[rr] = nv;
-        ++nseen;
-        if (fresh && v == nv) fresh = false;
-        m = __ballot(fresh);
-      }
-    };
-    for (int base = 0; base < w.total && nseen < min_frames; base += 64) {
-      const int qq = base + lane;
-      const int64_t c = (qq < w.total) ? window_cell<D>(w, qq, g, slab_t, p.w, p.w) : -1;
-      int b = 0, e = 0, cls = 0;
-      if (c >= 0 && ((occ_bits[c >> 5] >> (c & 31)) & 1u)) {
-        const CellRec<D> cr = crec[c];
-        b = cr.b;
-        e = cr.e;
-        cls = classify<D>(p, rec_boxA<D>(cr), rec_boxB(cr), g);
-      }
-      uint64_t pm = __ballot(cls != 0);
-      while (pm && nseen < min_frames) {
-        const int l = __ffsll((unsigned long long)pm) - 1;
-        pm &= pm - 1;
-        const int bb = __shfl(b, l), cl = __shfl(cls, l);
-        // a whole-cell hit in frame-id data is one frame: its first point says which
-        const int ee = (cl == 1 && integral) ? bb + 1 : __shfl(e, l);
-        for (int j0 = bb; j0 < ee && nseen < min_frames; j0 += 64) {
-          const int j = j0 + lane;
-          bool has = false;
-          int32_t v = 0;
-          if (j < ee) {
-            const float4 pj = pts[j];
-            if (cl == 1 || adjacent<D>(p, pj, g)) {
-              has = true;
-              v = np_i32(pj.w);
-            }
-          }
-          add(has, v);
-        }
-      }
-    }
-    if (lane == 0) core[s] = (nseen >= min_frames) ? 1 : 0;
-  }
-}
-
-// spos[orig] = sorted position (when the grid build did not write it)
-__global__ void k_inverse_perm(const int32_t* __restrict__ sorig, int64_t n,
-                               int32_t* __restrict__ spos) {
-  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n;
-       s += (int64_t)gridDim.x * blockDim.x)
-    spos[sorig[s]] = (int32_t)s;
-}
-
-// Border labels of the FIFO expansion (:340-367).  Clusters are drained one after another in
-// seed order, the seed being the component's minimum core index m (what ccmin holds).  A non-core
-// point p (original index P) is popped by cluster m -- and keeps the first such label -- iff it is
-// adjacent to a core point of m and either P > m (still unvisited when m's cores expand) or p is a
-// neighbour of the seed itself (the seed's neighbour list is queued whole, visited or not, :343).
-// Every qualifying m < P beats every m > P, so the first kind is a plain minimum and the second is
-// resolved smallest-first with one seed test per distinct m.  One wave per non-core point.
-template <int D>
-__global__ __launch_bounds__(kBlock) void k_label_fifo(const float4* __restrict__ pts,
-                                                      const int32_t* __restrict__ skey, Geom g,
-                                                      const CellRec<D>* __restrict__ crec,
-                                                      const uint32_t* __restrict__ occ_bits,
-                                                      const float2* __restrict__ slab_t,
-                                                      const int32_t* __restrict__ ccmin,
-                                                      const int32_t* __restrict__ rep,
-                                                      const int32_t* __restrict__ sorig,
-                                                      const int32_t* __restrict__ spos,
-                                                      MinRank cid,
-                                                      const int32_t* __restrict__ nc_list,
-                                                      const int32_t* __restrict__ nc_count,
-                                                      int32_t* __restrict__ labels) {
-  const int lane = threadIdx.x & 63;
-  const int64_t w0 = (int64_t)blockIdx.x * (kBlock / 64) + threadIdx.x / 64;
-  const int64_t nw = (int64_t)gridDim.x * (kBlock / 64);
-  const int64_t nq = *nc_count;
-  for (int64_t q = w0; q < nq; q += nw) {
-    const int s = nc_list[q];
-    const int P = sorig[s];
-    const int32_t key = skey[s];
-    int best_lt = INT_MAX, best_gt = INT_MAX;
-    if ((int64_t)key < g.cells) {
-      const float4 p = pts[s];
-      int cx, cy, cz;
-      decode_key<D>(key, g, cx, cy, cz);
-      const Window w = make_window<D, false>(cx, cy, cz, p.w, p.w, g, slab_t);
-      for (int base = 0; base < w.total; base += 64) {
-        const int qq = base + lane;
-        const int64_t c = (qq < w.total) ? window_cell<D>(w, qq, g, slab_t, p.w, p.w) : -1;
-        int b = 0, e = 0, cls = 0;
-        if (c >= 0 && ((occ_bits[c >> 5] >> (c & 31)) & 1u) && rep[c] >= 0) {
-          const CellRec<D> cr = crec[c];
-          b = cr.b;
-          e = cr.e;
-          cls = classify<D>(p, rec_boxA<D>(cr), rec_boxB(cr), g);
-        }
-        uint64_t pm = __ballot(cls != 0);
-        while (pm) {
-          const int l = __ffsll((unsigned long long)pm) - 1;
-          pm &= pm - 1;
-          const int bb = __shfl(b, l), ee = __shfl(e, l), cl = __shfl(cls, l);
-          for (int j0 = bb; j0 < ee; j0 += 64) {
-            const int j = j0 + lane;
-            int m = -1;
-            if (j < ee) {
-              m = ccmin[j];
-              if (m >= 0 && cl != 1 && !adjacent<D>(p, pts[j], g)) m = -1;
-            }
-            int lt = (m >= 0 && m < P) ? m : INT_MAX;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) lt = min(lt, __shfl_xor(lt, off));
-            best_lt = min(best_lt, lt);
-            if (best_lt != INT_MAX) continue;  // a smaller qualifying cluster is known
-            // m > P: the smallest not yet rejected whose seed is a neighbour of p
-            int cand = (m > P && m < best_gt) ? m : INT_MAX;
-            while (true) {
-              int mm = cand;
-#pragma unroll
-              for (int off = 32; off > 0; off >>= 1) mm = min(mm, __shfl_xor(mm, off));
-              if (mm == INT_MAX) break;
-              if (adjacent<D>(p, pts[spos[mm]], g)) {
-                best_gt = mm;
-                break;
-              }
-              if (cand == mm) cand = INT_MAX;
-            }
-          }
-        }
-      }
-    }
-    if (lane == 0) {
-      const int best = (best_lt != INT_MAX) ? best_lt : best_gt;
-      labels[P] = (best != INT_MAX) ? cid[best] : -1;
-    }
-  }
-}
+#include "stdbscan_label.inc"
+#include "stdbscan_frames.inc"
 
 struct Timer {
   bool on = false;
@@ -4349,6 +3305,17 @@ struct Timer {
       if (e) (void)hipEventDestroy(e);
   }
 };
+
+// A kernel form chosen at run time, its launch written once: f gets the template argument as an
+// std::integral_constant (f(std::true_type{}) / f(std::false_type{}); the grid's dimension 2 / 3).
+template <class F>
+auto with_bool(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
+template <class F>
+auto with_dim(int dim, F&& f) {
+  return dim == 2 ? f(std::integral_constant<int, 2>{}) : f(std::integral_constant<int, 3>{});
+}
 
 }  // namespace
 
@@ -4468,6 +3435,12 @@ struct DbscanState {
     if (!xy_points) return RPT_OK;
     set_error("%s: internal: this state's sorted points are xy-only", who);
     return RPT_EHIP;
+  }
+  // the sorted points as the kernels of one layout read or write them (XY only where
+  // xy_points: the allocation's first half)
+  template <bool XY>
+  Pt<XY>* points() const {
+    return reinterpret_cast<Pt<XY>*>(pts);
   }
   int64_t* stmp = nullptr;
   Timer tm;
@@ -4676,7 +3649,8 @@ int32_t DbscanState::build_t(const float* x, const float* y, const float* z, int
                       (int64_t)nx * ny <= kBucketCells && nt < (int64_t(1) << 31);
   // xy points: written by the slab writers only, every time finite (no isolated cell)
   xy_points = may_xy && bucket && D == 2 && hb.n_finite_t == n && xy_rule();
-  Pt<true>* pts_xy = reinterpret_cast<Pt<true>*>(pts);  // the allocation's first half
+  // (xy points: the writer fills slab_t from the slabs' own time values)
+  float2* const slab_t_w = xy_points ? slab_t : nullptr;
   if (bucket) {
     hipLaunchKernelGGL(k_slab_lo, dim3(grid_for(64 * (nt + 1), kBlock, 4096)), dim3(kBlock), 0,
                        st, t, n, g, slab_lo, occ_bits, (int64_t)(C1 / 32 + 2));
@@ -4709,9 +3683,10 @@ int32_t DbscanState::build_t(const float* x, const float* y, const float* z, int
       // split to fill the GPU) keep the one-block-per-slab scan (125 frames: 38 vs 53 us)
       RPT_HIP(hipFuncSetAttribute((const void*)k_slab_chunk_hist,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_bytes));
-      RPT_HIP(hipFuncSetAttribute(xy_points ? (const void*)k_slab_chunk_scatter<true>
-                                            : (const void*)k_slab_chunk_scatter<false>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_bytes));
+      const void* scatter = with_bool(
+          xy_points, [](auto xy) { return (const void*)k_slab_chunk_scatter<xy.value>; });
+      RPT_HIP(hipFuncSetAttribute(scatter, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)hist_bytes));
       hipLaunchKernelGGL(k_slab_chunk_hist, dim3((unsigned)(nt * CH)), dim3(kBucketBlock),
                          hist_bytes, st, x, y, stride, g, slab_lo, CH, hist_g);
       if (!coalesced_scan) {
@@ -4736,45 +3711,35 @@ int32_t DbscanState::build_t(const float* x, const float* y, const float* z, int
                            st, cell_root, P, nt, occ_base);
         RPT_CHECK_LAUNCH();
       }
-      if (xy_points)
-        hipLaunchKernelGGL(k_slab_chunk_scatter<true>, dim3((unsigned)(nt * CH)),
+      with_bool(xy_points, [&](auto xy) {
+        hipLaunchKernelGGL(k_slab_chunk_scatter<xy.value>, dim3((unsigned)(nt * CH)),
                            dim3(kBucketBlock), hist_bytes, st, x, y, stride, t, g, slab_lo, CH,
-                           hist_g, pts_xy, sorig, skey, spos_w, slab_t);
-      else
-        hipLaunchKernelGGL(k_slab_chunk_scatter<false>, dim3((unsigned)(nt * CH)),
-                           dim3(kBucketBlock), hist_bytes, st, x, y, stride, t, g, slab_lo, CH,
-                           hist_g, pts, sorig, skey, spos_w, (float2*)nullptr);
+                           hist_g, points<xy.value>(), sorig, skey, spos_w, slab_t_w);
+      });
     } else {
       // the fused K5's all-core cell minima from the counting sort when both LDS arrays fit 64 KiB
       bucket_allmin = k5_fused_path() && 2 * hist_bytes <= 65536 &&
                       ab().bucket_allmin != 0;  // (=0: from k_cell_box; A/B)
       const size_t lds = bucket_allmin ? 2 * hist_bytes : hist_bytes;
-      RPT_HIP(hipFuncSetAttribute(xy_points ? (const void*)k_slab_bucket<true>
-                                            : (const void*)k_slab_bucket<false>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      const void* bucket_fn =
+          with_bool(xy_points, [](auto xy) { return (const void*)k_slab_bucket<xy.value>; });
+      RPT_HIP(hipFuncSetAttribute(bucket_fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds));
 #ifdef RPT_AB
       if (ab().stats) {  // A/B diagnostics: blocks per CU the runtime admits
         int nb = -1;
-        if (xy_points)
-          (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_slab_bucket<true>,
-                                                             kBucketBlock, lds);
-        else
-          (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_slab_bucket<false>,
-                                                             kBucketBlock, lds);
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, bucket_fn, kBucketBlock, lds);
         std::fprintf(stderr, "[rpt stats] slab_bucket lds=%zu nx=%d ny=%d blocks_per_cu=%d\n", lds,
                      (int)nx, (int)ny, nb);
       }
 #endif
       auto* cmin_all =
           bucket_allmin ? reinterpret_cast<unsigned long long*>(cell_min_pair) : nullptr;
-      if (xy_points)
-        hipLaunchKernelGGL(k_slab_bucket<true>, dim3((unsigned)nt), dim3(kBucketBlock), lds, st,
-                           x, y, stride, t, g, slab_lo, pts_xy, sorig, skey, spos_w, cell_start,
-                           hpos, slab_occ, occ_bits, cmin_all, slab_t);
-      else
-        hipLaunchKernelGGL(k_slab_bucket<false>, dim3((unsigned)nt), dim3(kBucketBlock), lds, st,
-                           x, y, stride, t, g, slab_lo, pts, sorig, skey, spos_w, cell_start,
-                           hpos, slab_occ, occ_bits, cmin_all, (float2*)nullptr);
+      with_bool(xy_points, [&](auto xy) {
+        hipLaunchKernelGGL(k_slab_bucket<xy.value>, dim3((unsigned)nt), dim3(kBucketBlock), lds,
+                           st, x, y, stride, t, g, slab_lo, points<xy.value>(), sorig, skey,
+                           spos_w, cell_start, hpos, slab_occ, occ_bits, cmin_all, slab_t_w);
+      });
     }
     RPT_CHECK_LAUNCH();
     if (coalesced_scan) {
@@ -4821,11 +3786,12 @@ int32_t DbscanState::build_t(const float* x, const float* y, const float* z, int
     if (xy_points) {
       if constexpr (D == 2) {  // (the records' time fields from slab_t, written above)
         if (mixed)
-          hipLaunchKernelGGL((k_cell_box_mixed<2, true>), gm, dim3(kBlock), 0, st, pts_xy,
-                             cell_start, occ, n_occ_dev, g, mutual, cr, cmin_w, so_w, slab_t);
+          hipLaunchKernelGGL((k_cell_box_mixed<2, true>), gm, dim3(kBlock), 0, st,
+                             points<true>(), cell_start, occ, n_occ_dev, g, mutual, cr, cmin_w,
+                             so_w, slab_t);
         else
-          hipLaunchKernelGGL((k_cell_box<2, true>), gl, dim3(kBlock), 0, st, pts_xy, cell_start,
-                             occ, n_occ_dev, g, mutual, cr, cmin_w, so_w, slab_t);
+          hipLaunchKernelGGL((k_cell_box<2, true>), gl, dim3(kBlock), 0, st, points<true>(),
+                             cell_start, occ, n_occ_dev, g, mutual, cr, cmin_w, so_w, slab_t);
       }
     } else if (mixed)
       hipLaunchKernelGGL(k_cell_box_mixed<D>, gm, dim3(kBlock), 0, st, pts, cell_start, occ,
@@ -4918,12 +3884,10 @@ int32_t DbscanState::core_pass(hipStream_t st) {
       RPT_TRY(zero_n(st, 1, &n_cq));
       hipLaunchKernelGGL(k_core_cell_fast, dim3(tile_grid(n)), dim3(kBlock), 0, st, occ, n_occ,
                          g, cell_start, mutual, cflag, cq, n_cq);
-      if (dim == 2)
-        hipLaunchKernelGGL(k_core_cell_window<2>, dim3(wave_grid(n)), dim3(kBlock), 0, st, g,
-                           occ, rec<2>(), occ_bits, slab_t, cq, n_cq, cflag);
-      else
-        hipLaunchKernelGGL(k_core_cell_window<3>, dim3(wave_grid(n)), dim3(kBlock), 0, st, g,
-                           occ, rec<3>(), occ_bits, slab_t, cq, n_cq, cflag);
+      with_dim(dim, [&](auto d) {
+        hipLaunchKernelGGL(k_core_cell_window<d.value>, dim3(wave_grid(n)), dim3(kBlock), 0, st,
+                           g, occ, rec<d.value>(), occ_bits, slab_t, cq, n_cq, cflag);
+      });
       hipLaunchKernelGGL(k_core_fill<false>, dim3(tile_grid(n)), dim3(kBlock), 0, st, skey, n,
                          cflag, core, slow, n_slow);
     }
@@ -4955,14 +3919,11 @@ int32_t DbscanState::core_pass(hipStream_t st) {
                          (int)rs, occ, n_occ, rec<2>(), mutual, occ_bits, slab_t,
                          (int32_t*)nullptr, (int32_t*)nullptr, core, cm, slow, cq, n_slow, k5m,
                          cid);
-      if (xy_points)
-        hipLaunchKernelGGL(k_core_slow_masked<true>, dim3(wave_grid(n)), dim3(kBlock), 0, st,
-                           reinterpret_cast<const Pt<true>*>(pts), g, (int)rs, rec<2>(), occ,
-                           slow, cq, n_slow, k5m, cid, core, sorig, cm);
-      else
-        hipLaunchKernelGGL(k_core_slow_masked<false>, dim3(wave_grid(n)), dim3(kBlock), 0, st,
-                           pts, g, (int)rs, rec<2>(), occ, slow, cq, n_slow, k5m, cid, core,
-                           sorig, cm);
+      with_bool(xy_points, [&](auto xy) {
+        hipLaunchKernelGGL(k_core_slow_masked<xy.value>, dim3(wave_grid(n)), dim3(kBlock), 0, st,
+                           points<xy.value>(), g, (int)rs, rec<2>(), occ, slow, cq, n_slow, k5m,
+                           cid, core, sorig, cm);
+      });
     } else {
       hipLaunchKernelGGL(k_core_cells_oct<true>, dim3((grid_for(8 * n, kBlock, 8192) + 7) & ~7),
                          dim3(kBlock), 0, st, g, (int)rs, occ, n_occ, rec<2>(), mutual, occ_bits,
@@ -5008,12 +3969,10 @@ int32_t DbscanState::core_pass(hipStream_t st) {
     RPT_TRY(zero_n(st, 1, &n_cq));
     hipLaunchKernelGGL(k_core_cell_fast, dim3(tile_grid(n)), dim3(kBlock), 0, st, occ, n_occ, g,
                        cell_start, mutual, cflag, cq, n_cq);
-    if (dim == 2)
-      hipLaunchKernelGGL(k_core_cell_window<2>, dim3(wave_grid(n)), dim3(kBlock), 0, st, g, occ,
-                         rec<2>(), occ_bits, slab_t, cq, n_cq, cflag);
-    else
-      hipLaunchKernelGGL(k_core_cell_window<3>, dim3(wave_grid(n)), dim3(kBlock), 0, st, g, occ,
-                         rec<3>(), occ_bits, slab_t, cq, n_cq, cflag);
+    with_dim(dim, [&](auto d) {
+      hipLaunchKernelGGL(k_core_cell_window<d.value>, dim3(wave_grid(n)), dim3(kBlock), 0, st, g,
+                         occ, rec<d.value>(), occ_bits, slab_t, cq, n_cq, cflag);
+    });
   }
   hipLaunchKernelGGL(k_core_fill<true>, dim3(tile_grid(n)), dim3(kBlock), 0, st, skey, n, cflag,
                      core, slow, n_slow, sorig, cm, C);
@@ -5103,15 +4062,11 @@ int32_t DbscanState::union_pass(hipStream_t st, bool fused) {
         hipLaunchKernelGGL(k_cell_root_snapshot, dim3(grid_for(n, kBlock, 4096)), dim3(kBlock),
                            0, st, occ, n_occ, rep, parent, g.cells, uf_flags, cell_root);
       const int32_t* croot = snap ? (const int32_t*)cell_root : nullptr;
-      if (xy_points)
-        hipLaunchKernelGGL(k_union_listed<true>, dim3(gw), dim3(kBlock), 0, st,
-                           reinterpret_cast<const Pt<true>*>(pts), g, occ, rec<2>(), occ_bits,
-                           slab_t, core, rep, mutual, sorig, parent, uf_flags, pm, plist, pcount,
-                           croot, lstat_dev);
-      else
-        hipLaunchKernelGGL(k_union_listed<false>, dim3(gw), dim3(kBlock), 0, st, pts, g, occ,
-                           rec<2>(), occ_bits, slab_t, core, rep, mutual, sorig, parent, uf_flags,
-                           pm, plist, pcount, croot, lstat_dev);
+      with_bool(xy_points, [&](auto xy) {
+        hipLaunchKernelGGL(k_union_listed<xy.value>, dim3(gw), dim3(kBlock), 0, st,
+                           points<xy.value>(), g, occ, rec<2>(), occ_bits, slab_t, core, rep,
+                           mutual, sorig, parent, uf_flags, pm, plist, pcount, croot, lstat_dev);
+      });
     }
     else
       hipLaunchKernelGGL((k_union_cells<2, true>), dim3(gw), dim3(kBlock), 0, st, pts, g,
@@ -5126,12 +4081,13 @@ int32_t DbscanState::union_pass(hipStream_t st, bool fused) {
       hipLaunchKernelGGL(k_union<2>, dim3(gp), dim3(kBlock), 0, st, pts, skey, n, g, cell_start,
                          rec<2>(), slab_t, core, rep, mutual, sorig, parent);
   } else {
-    hipLaunchKernelGGL((k_union_cells<3, false>), dim3(gw), dim3(kBlock), 0, st, pts, g,
-                       cell_start, occ, n_occ, rec<3>(), occ_bits, slab_t, core, rep, mutual, sorig,
-                       parent, uf_flags);
-    hipLaunchKernelGGL((k_union_cells<3, true>), dim3(gw), dim3(kBlock), 0, st, pts, g,
-                       cell_start, occ, n_occ, rec<3>(), occ_bits, slab_t, core, rep, mutual, sorig,
-                       parent, uf_flags);
+    auto cells_pass = [&](auto partial) {  // (k_union_cells' PARTIAL: false, then true)
+      hipLaunchKernelGGL((k_union_cells<3, partial.value>), dim3(gw), dim3(kBlock), 0, st, pts, g,
+                         cell_start, occ, n_occ, rec<3>(), occ_bits, slab_t, core, rep, mutual,
+                         sorig, parent, uf_flags);
+    };
+    cells_pass(std::false_type{});
+    cells_pass(std::true_type{});
     hipLaunchKernelGGL(k_union<3>, dim3(gp), dim3(kBlock), 0, st, pts, skey, n, g, cell_start,
                        rec<3>(), slab_t, core, rep, mutual, sorig, parent);
   }
@@ -5217,14 +4173,11 @@ int32_t DbscanState::labels_local(int32_t* labels, rpt_stdbscan_stats* stats, hi
                        min_bits, W, min_pref);
     RPT_CHECK_LAUNCH();
     RPT_TRY(exclusive_scan_total_i32(min_pref, min_pref, W, st));
-    if (spos_on)
-      hipLaunchKernelGGL(k_label_core_cells<true>, dim3(glc), dim3(kBlock), 0, st, skey, core,
-                         slab, n, C, cell_min, mr, labels, nc_list, nc_count, cid + n,
-                         n_clusters_ptr());
-    else
-      hipLaunchKernelGGL(k_label_core_cells<false>, dim3(glc), dim3(kBlock), 0, st, skey, core,
-                         sorig, n, C, cell_min, mr, labels, nc_list, nc_count, cid + n,
-                         n_clusters_ptr());
+    with_bool(spos_on, [&](auto orig) {  // (ORIG: perm = spos, else sorig)
+      hipLaunchKernelGGL(k_label_core_cells<orig.value>, dim3(glc), dim3(kBlock), 0, st, skey,
+                         core, orig.value ? slab : sorig, n, C, cell_min, mr, labels, nc_list,
+                         nc_count, cid + n, n_clusters_ptr());
+    });
   } else {
     // also the per-cell smallest keys (k_cell_min_key fused; cell_min filled with INT_MAX by
     // cluster_ids' first kernel) and nc_count cleared
@@ -5377,16 +4330,12 @@ int32_t DbscanState::labels_global(const int64_t* rep_orig, const int64_t* reps,
                        MinRank{nullptr, nullptr}, nc_list, nc_count, labels);
   else
 #endif
-  if (dim == 2)
-    hipLaunchKernelGGL((k_label<2, true, 32>),
-                       dim3(wave_grid(n)), dim3(kBlock), 0, st, pts, skey, g,
-                       rec<2>(), occ_bits, slab_t, slab, cell_min, mutual, sorig,
-                       MinRank{nullptr, nullptr}, nc_list, nc_count, labels);
-  else
-    hipLaunchKernelGGL((k_label<3, true, 64>),
-                       dim3(wave_grid(n)), dim3(kBlock), 0, st, pts, skey, g,
-                       rec<3>(), occ_bits, slab_t, slab, cell_min, mutual, sorig,
-                       MinRank{nullptr, nullptr}, nc_list, nc_count, labels);
+  with_dim(dim, [&](auto d) {  // (W: a point per half-wave in 2-D, per wave in 3-D)
+    hipLaunchKernelGGL((k_label<d.value, true, d.value == 2 ? 32 : 64>), dim3(wave_grid(n)),
+                       dim3(kBlock), 0, st, pts, skey, g, rec<d.value>(), occ_bits, slab_t, slab,
+                       cell_min, mutual, sorig, MinRank{nullptr, nullptr}, nc_list, nc_count,
+                       labels);
+  });
   RPT_CHECK_LAUNCH();
   return RPT_OK;
 }
@@ -5416,22 +4365,18 @@ int32_t DbscanState::frames_pass(int32_t min_frames, hipStream_t st) {
     // offsets of int32(t) within +-31 of the point's own frame fit the 64-bit set (|dt| <=
     // eps_t <= 30); larger windows list the distinct frames instead
     const bool small = (double)g.epst <= 30.0;
-    if (dim == 2 && small)
-      hipLaunchKernelGGL(k_frames_points<2>, dim3(wave_grid(n)), dim3(kBlock), 0, st, pts, skey, g,
-                         rec<2>(), occ_bits, slab_t, one_frame_cells, (int)min_frames, list,
-                         count, core);
-    else if (small)
-      hipLaunchKernelGGL(k_frames_points<3>, dim3(wave_grid(n)), dim3(kBlock), 0, st, pts, skey, g,
-                         rec<3>(), occ_bits, slab_t, one_frame_cells, (int)min_frames, list,
-                         count, core);
-    else if (dim == 2)
-      hipLaunchKernelGGL(k_frames_points_list<2>, dim3(wave_grid(n)), dim3(kBlock), 0, st, pts,
-                         skey, g, rec<2>(), occ_bits, slab_t, one_frame_cells,
-                         (int)min_frames, list, count, core);
+    if (small)
+      with_dim(dim, [&](auto d) {
+        hipLaunchKernelGGL(k_frames_points<d.value>, dim3(wave_grid(n)), dim3(kBlock), 0, st, pts,
+                           skey, g, rec<d.value>(), occ_bits, slab_t, one_frame_cells,
+                           (int)min_frames, list, count, core);
+      });
     else
-      hipLaunchKernelGGL(k_frames_points_list<3>, dim3(wave_grid(n)), dim3(kBlock), 0, st, pts,
-                         skey, g, rec<3>(), occ_bits, slab_t, one_frame_cells,
-                         (int)min_frames, list, count, core);
+      with_dim(dim, [&](auto d) {
+        hipLaunchKernelGGL(k_frames_points_list<d.value>, dim3(wave_grid(n)), dim3(kBlock), 0, st,
+                           pts, skey, g, rec<d.value>(), occ_bits, slab_t, one_frame_cells,
+                           (int)min_frames, list, count, core);
+      });
   }
   RPT_CHECK_LAUNCH();
   return RPT_OK;
@@ -5448,14 +4393,11 @@ int32_t DbscanState::labels_fifo(int32_t* labels, rpt_stdbscan_stats* stats, hip
   const MinRank mr{min_bits, min_pref};
   hipLaunchKernelGGL(k_label_core_orig, dim3((grid_for(n, kBlock * kPU, 2048) + 7) & ~7),
                      dim3(kBlock), 0, st, ccmin, n, spos, mr, labels);
-  if (dim == 2)
-    hipLaunchKernelGGL((k_label_fifo<2>), dim3(wave_grid(n)), dim3(kBlock), 0, st, pts, skey, g,
-                       rec<2>(), occ_bits, slab_t, ccmin, rep, sorig, spos, mr, nc_list,
+  with_dim(dim, [&](auto d) {
+    hipLaunchKernelGGL(k_label_fifo<d.value>, dim3(wave_grid(n)), dim3(kBlock), 0, st, pts, skey,
+                       g, rec<d.value>(), occ_bits, slab_t, ccmin, rep, sorig, spos, mr, nc_list,
                        nc_count, labels);
-  else
-    hipLaunchKernelGGL((k_label_fifo<3>), dim3(wave_grid(n)), dim3(kBlock), 0, st, pts, skey, g,
-                       rec<3>(), occ_bits, slab_t, ccmin, rep, sorig, spos, mr, nc_list,
-                       nc_count, labels);
+  });
   RPT_CHECK_LAUNCH();
   tm.mark();
   int32_t ncl = 0;
@@ -5486,6 +4428,20 @@ static int32_t check_args(const float* x, const float* y, const float* z, int64_
 static std::mutex g_state_mu;
 // per (device, stream), for the fused single-call path
 static std::vector<std::pair<std::pair<int, hipStream_t>, DbscanState*>> g_states;
+// *S: the state of (the current device, st), created at its first use
+static int32_t state_for(hipStream_t st, DbscanState** S) {
+  int dev = 0;
+  RPT_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lk(g_state_mu);
+  *S = nullptr;
+  for (auto& e : g_states)
+    if (e.first.first == dev && e.first.second == st) *S = e.second;
+  if (!*S) {
+    *S = new DbscanState();
+    g_states.push_back({{dev, st}, *S});
+  }
+  return RPT_OK;
+}
 
 int32_t stdbscan(const float* x, const float* y, const float* z, int64_t stride, const float* t,
                  int64_t n, double eps_space, double eps_time, int32_t min_samples,
@@ -5495,19 +4451,8 @@ int32_t stdbscan(const float* x, const float* y, const float* z, int64_t stride,
     set_error("rpt_stdbscan: null labels");
     return RPT_EINVAL;
   }
-  int dev = 0;
-  RPT_HIP(hipGetDevice(&dev));
   DbscanState* S;
-  {
-    std::lock_guard<std::mutex> lk(g_state_mu);
-    S = nullptr;
-    for (auto& e : g_states)
-      if (e.first.first == dev && e.first.second == st) S = e.second;
-    if (!S) {
-      S = new DbscanState();
-      g_states.push_back({{dev, st}, S});
-    }
-  }
+  RPT_TRY(state_for(st, &S));
   S->may_xy = stats != nullptr;  // (with stats: union_pass runs fused)
   RPT_TRY(S->build(x, y, z, stride, t, n, eps_space, eps_time, min_samples,
                    stats && stats->timing, st));
@@ -5536,19 +4481,8 @@ int32_t stdbscan_denoise(const float* x, const float* y, const float* t, int64_t
               64 * kFramesPerLane);
     return RPT_ENOTSUP;
   }
-  int dev = 0;
-  RPT_HIP(hipGetDevice(&dev));
   DbscanState* S;
-  {
-    std::lock_guard<std::mutex> lk(g_state_mu);
-    S = nullptr;
-    for (auto& e : g_states)
-      if (e.first.first == dev && e.first.second == st) S = e.second;
-    if (!S) {
-      S = new DbscanState();
-      g_states.push_back({{dev, st}, S});
-    }
-  }
+  RPT_TRY(state_for(st, &S));
   RPT_TRY(S->build(x, y, nullptr, 1, t, n, eps_space, eps_time, min_samples,
                    stats && stats->timing, st));
   if (S->degenerate) {
@@ -5612,19 +4546,8 @@ int32_t stdbscan_deferred(const float* x, const float* y, const float* z, int64_
     set_error("stdbscan_deferred: null argument");
     return RPT_EINVAL;
   }
-  int dev = 0;
-  RPT_HIP(hipGetDevice(&dev));
   DbscanState* S;
-  {
-    std::lock_guard<std::mutex> lk(g_state_mu);
-    S = nullptr;
-    for (auto& e : g_states)
-      if (e.first.first == dev && e.first.second == st) S = e.second;
-    if (!S) {
-      S = new DbscanState();
-      g_states.push_back({{dev, st}, S});
-    }
-  }
+  RPT_TRY(state_for(st, &S));
   S->given_bounds = host_bounds;
   S->may_xy = true;
   const int32_t sb = S->build(x, y, z, stride, t, n, eps_space, eps_time, min_samples,
