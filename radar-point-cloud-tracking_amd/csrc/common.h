@@ -117,7 +117,7 @@ int32_t exclusive_scan_total_i32(const int32_t* in, int32_t* out, int64_t n, hip
 
 // Back-to-back copy of up to kPackMax device arrays (sizes in 4-byte words) into dst.
 constexpr int kPackMax = 10;
-// Point-set bounds of the ST-DBSCAN grid build (k_bounds in stdbscan.hip; also produced by the
+// Point-set bounds of the ST-DBSCAN grid build (k_bounds, stdbscan_grid.inc; also produced by the
 // fused land compaction, land.hip): ordered-u32 (sign-flipped float bits) minima / maxima.
 struct Bounds {
   uint32_t mn[4];   // ordered-u32 minima of x, y, z, t (t over finite values only)
@@ -128,7 +128,7 @@ struct Bounds {
   int32_t t_descends;     // some t[i] < t[i-1]: the points are not in time order
 };
 
-// Device accumulator of a Bounds partial with k_bounds' semantics (stdbscan.hip), for kernels
+// Device accumulator of a Bounds partial with k_bounds' semantics (stdbscan_grid.inc), for kernels
 // that produce the ST-DBSCAN bounds of points they write anyway (the shard window).  add() per
 // point (t_prev: the previous point's t in the set's order, has_prev false for the first point),
 // then block_store() by EVERY thread of a block of kBoundsBlock threads: one partial per block,

@@ -1,6 +1,7 @@
 // A/B-only kernel forms of stdbscan.hip: included (inside its anonymous namespace, by
 // stdbscan_label.inc after k_label) only by the A/B build (-DRPT_AB, librpt_ab.so), never
-// compiled into librpt.so.
+// compiled into librpt.so.  Reads stdbscan_shared.inc and, from K6 (stdbscan_union.inc), the
+// union-find helpers (uf_*).
 // Each was measured slower than the shipped form and stays selectable for same-box comparisons
 // (DESIGN.md "A/B switches"): RPT_K5_MODE=1/2 (k_core_slow_cells), RPT_K5_TILES=1 (k_row_occ +
 // k_core_tiles), RPT_UF_COMPRESS=1 (k_compress), RPT_K7_TILES=1 (k_label_tiles).

@@ -3,6 +3,8 @@
 // frames_pass reads the sorted points, skey, the cell records, occ / occ_bits and slab_t, keeps
 // its per-cell result in fok and its point queue in nc_list, and demotes core flags; labels_fifo
 // reads ccmin, rep, sorig and the inverse permutation (slab) and writes the caller's labels.
+//   frames_pass: k_frames_cells, k_frames_queue, k_frames_points / k_frames_points_list
+//   labels_fifo: k_inverse_perm, k_label_core_orig, k_label_fifo
 
 // ---------------------------------------------------------------- denoise variant (O8)
 // PointCloudWorkF/stdbscan_denoising_pipeline.py:264-369.  A point is core when it has

@@ -5,7 +5,15 @@
 // records and the sorted points.  Writes cell_root, the component minima (ccmin, or cell_min per
 // occupied cell on the per-cell path), min_bits / min_pref (MinRank; the cluster count at
 // n_clusters_ptr()), the non-core queue (nc_list, its count at nc_list[n]) and the caller's
-// labels.  The A/B-only forms (stdbscan_ab.inc) are included after k_label.
+// labels.  Reads stdbscan_shared.inc and, from K6 (stdbscan_union.inc), the union-find helpers
+// (uf_*).  The A/B-only forms (stdbscan_ab.inc) are included after k_label.
+// Cluster id = rank of the component minimum among all minima (MinRank); core: own id; non-core:
+// min id over adjacent core points, else -1.
+//   local, per-cell path (cell_comp): k_cell_comp, k_word_popc, scan, k_label_core_cells
+//   local, otherwise: k_cell_roots, k_ccmin, k_word_popc, scan, k_label_core(_orig)
+//   then k_label over the queued non-core points
+//   global: k_cell_roots, k_ccmin_global, k_label_global_orig, k_label_global_core, k_label
+//   phased: k_core_to_orig, k_core_from_orig, k_comp_out, k_comp_out_edges
 
 __global__ __launch_bounds__(kBlock) void k_fill_i32(int32_t* p, int64_t n, int32_t v) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
