@@ -30,6 +30,9 @@
  *   rpt_text_rows_write              and np.savetxt(fmt="%.6f,%.6f,%.6f,%d") of write_labels_csv :79-81;
  *                                    the float32 to_csv rows of convert_single_csv processors/cartesian.py:46-53
  *   rpt_float32_repr                 np.float32(v).astype(str) (host; the code of that layout)
+ *   rpt_text_rows_index /            the vertex rows of load_ply radar_pipeline/core/loaders.py:149-220
+ *   rpt_text_rows_parse              (3_stdbscan_point_clouds.py:38-79): np.float32(float(token)) per token
+ *   rpt_decimal_parse_host           the per-token code of that parser on the host (no GPU)
  *   rpt_segment_percentile99 /       normalize_intensity PointCloudWork/5_gain_fusion_ply_builder.py:276-289
  *   rpt_heat_colors                  and intensity_to_rgb :292-327, per segment (frame) of one array;
  *   (RPT_TEXT_PLY4)                  the np.savetxt rows of write_ply_fast :370-403
@@ -296,6 +299,45 @@ int32_t rpt_text_rows_write(int32_t layout, const float* x, const float* y, cons
  * NaN and inf give len 0 and an all-NUL slot. */
 #define RPT_FLOAT32_REPR_SLOT 20
 int32_t rpt_float32_repr(const float* v, int64_t n, char* out /*[n][20]*/, int32_t* len /*[n]*/);
+
+/* ---- ASCII rows of decimal numbers -> float32 columns (the vertex lines of load_ply) --------
+ * The reverse of the text rows above: text (dev u8 [nbytes]) holds lines of blank-separated
+ * decimal tokens; the first n_rows lines are parsed into out (dev f32 [n_cols][n_rows], column
+ * major), every value np.float32(float(token)) bit for bit: the correctly rounded double of the
+ * token, then the float64 -> float32 cast (two roundings; csrc/parse32.h).
+ * Domain of a token: [+-]? digits[.digits*] or .digits; with leading zeros removed at most 19
+ * digits, their integer m <= 2^53, at most 22 digits behind the point.  Then double(m) / 10^f is
+ * one exact-operand IEEE division.  Domain of the text: only the bytes "0-9 + - . space tab \r
+ * \n", every \r followed by \n, tokens separated by runs of space / tab, lines ended by \n or
+ * \r\n (the last of the n_rows lines may end at the end of the text), at least n_rows lines,
+ * each of the first n_rows holding exactly n_cols tokens; nbytes < 2^32, 1 <= n_cols <= 16.
+ * Lines behind the n_rows-th are not parsed.  Whatever is outside (an exponent, nan, inf, other
+ * bytes, a ragged or blank row, too few lines) is COUNTED, never an error: a caller that sees a
+ * non-zero count or too few lines discards out and reads the text on the host.  No kernel reads
+ * outside [text, text + nbytes) or writes outside its outputs, whatever the bytes hold.
+ * rpt_text_rows_index: row_start (dev u32 [n_rows + 1]) = byte offset of the start of line j for
+ * j <= n_rows (row_start[n_rows] = nbytes when the last row ends the text); entries of lines
+ * that do not exist are 0xffffffff.  *lines_found_host = lines in the whole text (a last line
+ * without \n counts), *n_unsupported_host = bytes outside the set above plus \r without \n.
+ * Synchronises once.
+ * rpt_text_rows_parse: the rows between row_start[i] and row_start[i + 1] into out;
+ * *n_unsupported_host = rows with another token count than n_cols, a token outside the domain,
+ * more than 6128 bytes, or offsets that are not ascending inside the text.  Synchronises once.
+ * Both return RPT_ENOTSUP for nbytes or n_rows >= 2^32, the second also for n_cols outside
+ * 1..16.  rpt_text_tile_bytes (host only): the bytes one block of the index passes takes. */
+int32_t rpt_text_rows_index(const uint8_t* text /*dev*/, int64_t nbytes, int64_t n_rows,
+                            uint32_t* row_start /*dev [n_rows + 1]*/, int64_t* lines_found_host,
+                            int64_t* n_unsupported_host, void* stream);
+int32_t rpt_text_rows_parse(const uint8_t* text /*dev*/, int64_t nbytes,
+                            const uint32_t* row_start /*dev*/, int64_t n_rows, int32_t n_cols,
+                            float* out /*dev [n_cols][n_rows]*/, int64_t* n_unsupported_host,
+                            void* stream);
+int64_t rpt_text_tile_bytes(void);
+
+/* Host only (no GPU): the parser's per-token code.  Token i is text[tok_off[i] .. + tok_len[i]);
+ * ok[i] = 1 and out[i] = its value when it is inside the domain, else ok[i] = 0 and out[i] = 0. */
+int32_t rpt_decimal_parse_host(const char* text, const int64_t* tok_off, const int32_t* tok_len,
+                               int64_t n, float* out /*[n]*/, uint8_t* ok /*[n]*/);
 
 /* ---- gain-fusion colours (5_gain_fusion_ply_builder.py normalize_intensity :276-289,
  * intensity_to_rgb :292-327) ----------------------------------------------------------------

@@ -80,6 +80,12 @@ int32_t text_rows_size(int32_t layout, const float* x, const float* y, const flo
 int32_t text_rows_write(int32_t layout, const float* x, const float* y, const float* z,
                         const void* tail, int64_t n, const int64_t* row_offsets, uint8_t* out,
                         int64_t out_bytes, hipStream_t st);
+int64_t text_tile_bytes();
+int32_t text_rows_index(const uint8_t* text, int64_t nbytes, int64_t n_rows, uint32_t* row_start,
+                        int64_t* lines_found_host, int64_t* n_bad_host, hipStream_t st);
+int32_t text_rows_parse(const uint8_t* text, int64_t nbytes, const uint32_t* row_start,
+                        int64_t n_rows, int32_t n_cols, float* out, int64_t* n_bad_host,
+                        hipStream_t st);
 }  // namespace rpt
 
 struct rpt_dbscan {
@@ -367,6 +373,46 @@ int32_t rpt_text_rows_write(int32_t layout, const float* x, const float* y, cons
   }
   return rpt::text_rows_write(layout, x, y, z, tail, n, row_offsets, out, out_bytes,
                               rpt::as_stream(stream));
+}
+
+int64_t rpt_text_tile_bytes(void) { return rpt::text_tile_bytes(); }
+
+int32_t rpt_text_rows_index(const uint8_t* text, int64_t nbytes, int64_t n_rows,
+                            uint32_t* row_start, int64_t* lines_found_host,
+                            int64_t* n_unsupported_host, void* stream) {
+  rpt::clear_error();
+  if (nbytes < 0 || n_rows < 0 || !row_start || !lines_found_host || !n_unsupported_host ||
+      (nbytes > 0 && !text)) {
+    rpt::set_error("rpt_text_rows_index: bad arguments");
+    return RPT_EINVAL;
+  }
+  if (nbytes >= (int64_t(1) << 32) || n_rows >= (int64_t(1) << 32)) {  // uint32 offsets
+    rpt::set_error("rpt_text_rows_index: nbytes=%lld, n_rows=%lld exceed the 32-bit offsets",
+                   (long long)nbytes, (long long)n_rows);
+    return RPT_ENOTSUP;
+  }
+  return rpt::text_rows_index(text, nbytes, n_rows, row_start, lines_found_host,
+                              n_unsupported_host, rpt::as_stream(stream));
+}
+
+int32_t rpt_text_rows_parse(const uint8_t* text, int64_t nbytes, const uint32_t* row_start,
+                            int64_t n_rows, int32_t n_cols, float* out,
+                            int64_t* n_unsupported_host, void* stream) {
+  rpt::clear_error();
+  if (nbytes < 0 || n_rows < 0 || !n_unsupported_host ||
+      (n_rows > 0 && (!row_start || !out || (nbytes > 0 && !text)))) {
+    rpt::set_error("rpt_text_rows_parse: bad arguments");
+    return RPT_EINVAL;
+  }
+  if (nbytes >= (int64_t(1) << 32) || n_rows >= (int64_t(1) << 32) || n_cols < 1 ||
+      n_cols > 16) {
+    rpt::set_error("rpt_text_rows_parse: nbytes=%lld, n_rows=%lld, n_cols=%d outside the "
+                   "32-bit offsets / 1..16 columns", (long long)nbytes, (long long)n_rows,
+                   (int)n_cols);
+    return RPT_ENOTSUP;
+  }
+  return rpt::text_rows_parse(text, nbytes, row_start, n_rows, n_cols, out,
+                              n_unsupported_host, rpt::as_stream(stream));
 }
 
 int32_t rpt_cluster_summaries(const int32_t* labels, const float* x, const float* y,

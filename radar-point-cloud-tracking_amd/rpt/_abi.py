@@ -259,6 +259,11 @@ _SIGS = [
     ("rpt_text_rows_write", C.c_int32,
      [C.c_int32, vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int64, vp]),
     ("rpt_float32_repr", C.c_int32, [vp, C.c_int64, vp, vp]),
+    ("rpt_text_rows_index", C.c_int32, [vp, C.c_int64, C.c_int64, vp, c_i64p, c_i64p, vp]),
+    ("rpt_text_rows_parse", C.c_int32,
+     [vp, C.c_int64, vp, C.c_int64, C.c_int32, vp, c_i64p, vp]),
+    ("rpt_text_tile_bytes", C.c_int64, []),
+    ("rpt_decimal_parse_host", C.c_int32, [vp, vp, vp, C.c_int64, vp, vp]),
     ("rpt_segment_percentile99", C.c_int32, [vp, C.c_int64, vp, C.c_int64, vp, vp, vp]),
     ("rpt_heat_colors", C.c_int32,
      [vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int32, vp, vp, vp]),

@@ -144,10 +144,94 @@ def detect_csv_format(path: Path) -> str:
     return "radar"
 
 
-def load_ply(path: Path) -> PointCloud:
+_PLY_HEADER_PREFIX = 1 << 16  # bytes of the file the device path looks for the header in
+
+
+def _ply_header(raw: bytes):
+    """The header loop of the host reader over the prefix ``raw``, line by line in bytes:
+    (element vertex count, property names, byte offset of the body), or None when the prefix does
+    not hold a header the device path takes (no ``end_header``, a non-ASCII byte, a ``\\r`` that
+    is not part of ``\\r\\n``, a count that is no integer): the host reader then decides."""
+    n = None
+    props = []
+    pos = 0
+    first = True
+    while True:
+        nl = raw.find(b"\n", pos)
+        if nl < 0:
+            return None
+        line = raw[pos:nl]
+        pos = nl + 1
+        if b"\r" in line[:-1]:
+            return None  # universal newlines would end a line here
+        try:
+            s = line.decode("ascii").strip()
+        except UnicodeDecodeError:
+            return None
+        if first and not s.startswith("ply"):
+            return None
+        first = False
+        if s.startswith("element vertex"):
+            try:
+                n = int(s.split()[-1])
+            except ValueError:
+                return None
+        elif s.startswith("property"):
+            props.append(s.split()[-1])
+        elif s == "end_header":
+            return (n, props, pos) if n is not None else None
+
+
+def _load_ply_device(path: Path, text):
+    """load_ply with the vertex rows parsed on the device: (PointCloud, None), or (None, reason)
+    when the file is outside that path's domain."""
+    raw = path.read_bytes()
+    hdr = _ply_header(raw[:_PLY_HEADER_PREFIX])
+    if hdr is None:
+        return None, "header"
+    n, props, body = hdr
+    ix = {p: k for k, p in enumerate(props)}
+    rgb = [ix[c] for c in ("red", "green", "blue")] if {"red", "green", "blue"} <= ix.keys() \
+        else []
+    if not {"x", "y", "z"} <= ix.keys():
+        return None, "header"
+    cols, reason = text.parse_rows_reason(memoryview(raw)[body:], n)
+    if cols is None:
+        return None, reason
+    if max([ix["x"], ix["y"], ix["z"], *rgb]) >= cols.shape[0]:
+        return None, "header"  # a property without a column: the host reader's IndexError
+    data = cols.cpu().numpy()
+    colors = np.stack([data[k] for k in rgb], axis=1).astype(np.uint8) if rgb else None
+    return PointCloud(x=data[ix["x"]], y=data[ix["y"]], z=data[ix["z"]], colors=colors), None
+
+
+def load_ply(path: Path, device: Optional[bool] = None,
+             info: Optional[dict] = None) -> PointCloud:
     """ASCII PLY reader with x/y/z and optional uchar RGB (loaders.py:149-220 /
-    3_stdbscan_point_clouds.py:38-79)."""
+    3_stdbscan_point_clouds.py:38-79).
+
+    With a GPU the vertex rows are parsed on the device (rpt.core.text.parse_rows): plain decimal
+    tokens, every value ``np.float32(float(token))`` bit for bit.  A file outside that domain (an
+    exponent, nan, a ragged row, too few lines, non-ASCII bytes, ...), ``device=False`` and a host
+    without a GPU take the host reader below, which IS the reference's code: same values, same
+    exceptions.  ``info`` (a dict) receives ``parser`` ("device" / "host") and, for "host", the
+    ``reason``: no_gpu, forced, header, bytes, lines, rows or size."""
     path = Path(path)
+    reason = "forced"
+    if device is not False:
+        from . import text
+
+        reason = "no_gpu"
+        if text.gpu_visible():
+            cloud, reason = _load_ply_device(path, text)
+            if cloud is not None:
+                if info is not None:
+                    info["parser"] = "device"
+                    info.pop("reason", None)
+                return cloud
+    if info is not None:
+        info["parser"] = "host"
+        info["reason"] = reason
     with path.open("r", encoding="utf-8") as fh:
         lines = fh.readlines()
     if not lines or not lines[0].strip().startswith("ply"):

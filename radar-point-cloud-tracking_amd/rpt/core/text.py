@@ -18,6 +18,12 @@ A fourth are the ``"%.4f %.4f %.4f %d %d %d"`` rows ``np.savetxt`` writes in ``w
 the row offsets, so that one launch over a group of frames can be cut into one slice per file.
 
 Torch device tensors in -> a device ``uint8`` tensor out; numpy in -> ``bytes`` out.
+
+The other way, ``parse_rows`` reads rows of plain decimal tokens (the vertex lines ``load_ply``
+meets, radar_pipeline/core/loaders.py:149-220) into float32 columns on the device
+(csrc/ply_parse.hip, csrc/parse32.h): ``np.float32(float(token))`` bit for bit inside a narrow
+domain, ``None`` outside it -- the caller's host reader then produces the reference's value or
+exception.
 """
 from __future__ import annotations
 
@@ -269,6 +275,130 @@ def write_text(fh, text) -> None:
             events[k % 2].synchronize()
             fh.write(memoryview(bufs[k % 2].numpy())[:cnt])
             cnt = nxt
+
+
+# ---- text -> device columns (the reverse way) -----------------------------------------------------
+
+PARSE_MAX_COLS = 16
+_FIRST_LINE_PREFIX = 8192  # bytes of a device text looked at for the first row's token count
+
+
+def text_to_device(text, dev: torch.device) -> torch.Tensor:
+    """Host bytes as a device uint8 tensor, in pieces through the two pinned staging buffers (the
+    host copy of piece k+1 into its buffer runs while piece k travels): write_text the other way."""
+    src = np.frombuffer(text, dtype=np.uint8)
+    n = src.size
+    out = torch.empty(n, dtype=torch.uint8, device=dev)
+    if n == 0:
+        return out
+    pieces = -(-n // _COPY_CHUNK)
+    size, bufs = _staging(n, min(pieces, 2))
+    events = [torch.cuda.Event() for _ in bufs]
+    with torch.cuda.device(dev):
+        for k in range(pieces):
+            lo = k * size
+            cnt = min(size, n - lo)
+            if k >= 2:
+                events[k % 2].synchronize()  # the buffer's previous piece has left it
+            bufs[k % 2].numpy()[:cnt] = src[lo:lo + cnt]
+            out[lo:lo + cnt].copy_(bufs[k % 2][:cnt], non_blocking=True)
+            events[k % 2].record()
+        for ev in events:
+            ev.synchronize()  # the staging buffers are free for the module's next user
+    return out
+
+
+def parse_rows_device(text: torch.Tensor, n_rows: int, n_cols: int):
+    """The first n_rows lines of a contiguous device uint8 text as (float32 [n_cols, n_rows] on
+    the device, None), or (None, reason) when the text is outside the kernels' domain: "size"
+    (2**32 bytes or more, no row, n_cols outside 1..16), "bytes" (a byte that is none of
+    ``0-9 + - . space tab \\r \\n``, a lone ``\\r``), "lines" (fewer than n_rows lines), "rows" (a
+    row with another token count or a token outside csrc/parse32.h's domain)."""
+    nbytes = text.numel()
+    if n_rows < 1 or not 1 <= n_cols <= PARSE_MAX_COLS or nbytes >= 1 << 32:
+        return None, "size"
+    if n_rows > nbytes:  # a line takes a byte at least
+        return None, "lines"
+    dev = text.device
+    if text.data_ptr() % 16:  # a slice: the kernels' 16-byte loads want an aligned base
+        text = text.clone()
+    lib = _abi.load()
+    found = C.c_int64(0)
+    bad = C.c_int64(0)
+    with torch.cuda.device(dev):
+        st = stream_handle(dev)
+        row_start = torch.empty(n_rows + 1, dtype=torch.int32, device=dev)  # uint32 offsets
+        _abi.check(lib.rpt_text_rows_index(text.data_ptr(), nbytes, n_rows, row_start.data_ptr(),
+                                           C.byref(found), C.byref(bad), st),
+                   "rpt_text_rows_index")
+        if bad.value:
+            return None, "bytes"
+        if found.value < n_rows:
+            return None, "lines"
+        out = torch.empty((n_cols, n_rows), dtype=torch.float32, device=dev)
+        _abi.check(lib.rpt_text_rows_parse(text.data_ptr(), nbytes, row_start.data_ptr(), n_rows,
+                                           n_cols, out.data_ptr(), C.byref(bad), st),
+                   "rpt_text_rows_parse")
+    if bad.value:
+        return None, "rows"
+    return out, None
+
+
+def _text_len(text) -> int:
+    return text.numel() if is_torch(text) else len(text)
+
+
+def _first_line_tokens(text) -> int:
+    """Token count of the first line (split on the host, from a prefix of the text)."""
+    head = text[:_FIRST_LINE_PREFIX]
+    head = head.cpu().numpy().tobytes() if is_torch(head) else bytes(head)
+    end = head.find(b"\n")
+    if end < 0 and _text_len(text) > _FIRST_LINE_PREFIX:
+        return 0  # a first row longer than the kernels stage: outside the domain anyway
+    return len((head if end < 0 else head[:end]).split())
+
+
+def parse_rows_reason(text, n_rows: int, n_cols: Optional[int] = None):
+    """parse_rows' work: (device float32 [n_cols, n_rows], None) or (None, reason)."""
+    if is_torch(text):
+        if text.dtype != torch.uint8 or text.ndim != 1:
+            raise ValueError("parse_rows: text must be a one-dimensional uint8 tensor")
+        on_device = text.is_cuda
+    else:
+        text = memoryview(text).cast("B")
+        on_device = False
+    if not on_device and not gpu_visible():
+        raise RuntimeError("parse_rows: no ROCm device (the host reader is load_ply's)")
+    n_rows = int(n_rows)
+    if n_cols is None:
+        n_cols = _first_line_tokens(text)
+    if on_device:
+        dev_text = text.contiguous()
+    else:
+        if n_rows < 1 or not 1 <= n_cols <= PARSE_MAX_COLS or _text_len(text) >= 1 << 32:
+            return None, "size"  # before the copy
+        dev = torch.device("cuda", torch.cuda.current_device())
+        dev_text = text_to_device(text.contiguous().numpy() if is_torch(text) else text, dev)
+    return parse_rows_device(dev_text, n_rows, int(n_cols))
+
+
+def parse_rows(text, n_rows: int, n_cols: Optional[int] = None,
+               as_tensor: Optional[bool] = None):
+    """The first ``n_rows`` lines of ``text`` -- blank-separated decimal tokens, ``n_cols`` a line
+    (None: as many as the first line holds) -- as float32 ``[n_cols, n_rows]``, every value
+    ``np.float32(float(token))`` bit for bit, parsed on the device (csrc/ply_parse.hip).  text:
+    bytes, a memoryview or a uint8 tensor on the host or the device.  Returns None when the text is
+    outside the kernels' domain (parse_rows_device): the caller then reads it on the host.
+    as_tensor: True returns a tensor (on the device for a device text), False a numpy array; by
+    default a tensor in gives a tensor out."""
+    want_torch = is_torch(text) if as_tensor is None else as_tensor
+    to_host = not (is_torch(text) and text.is_cuda)
+    out, _ = parse_rows_reason(text, n_rows, n_cols)
+    if out is None:
+        return None
+    if not want_torch:
+        return out.cpu().numpy()
+    return out.cpu() if to_host and as_tensor is None else out
 
 
 def text_to_host(text: torch.Tensor) -> memoryview:
