@@ -20,7 +20,7 @@ inline T ab_range(T v, T lo, T hi, T otherwise) {
 // an unset variable leaves the default.
 //   off iff 0: std::atoi(e) != 0      on iff 1: std::atoi(e) == 1
 #define RPT_AB_SWITCHES(X)                                                                        \
-  /* K1 (polar.hip, stack.cpp, shard.cpp) */                                                      \
+  /* K1 (polar.hip, the driver of the polar_*.inc kernels; stack.cpp, shard.cpp) */               \
   /* =0: K1 reads the echo twice (no staged kept samples from the count pass) */                  \
   X("RPT_K1_STAGE", k1_stage, bool, true, std::atoi(e) != 0)                                      \
   /* =0: the wave-per-group write instead of the persistent k_expand_write */                     \

@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "polar.h"
 
 namespace rpt {
 void release_scratch_current();
@@ -18,29 +19,6 @@ int32_t stdbscan_denoise(const float* x, const float* y, const float* t, int64_t
 int32_t stdbscan(const float* x, const float* y, const float* z, int64_t stride, const float* t,
                  int64_t n, double eps_space, double eps_time, int32_t min_samples,
                  int32_t* labels, rpt_stdbscan_stats* stats, hipStream_t st, int dim);
-int32_t polar_count(const void* echo, int32_t dt, int64_t n_files, int32_t rows, int32_t bins,
-                    float thr, int32_t stride, int64_t* row_prefix, int64_t* file_offsets,
-                    int64_t* total_host, hipStream_t st, uint32_t* entries);
-int32_t polar_write(const void* echo, int32_t dt, int64_t n_files, int32_t rows, int32_t bins,
-                    const float* scale, const float* cos_t, const float* sin_t,
-                    const int32_t* gain, float thr, int32_t stride, const int64_t* row_prefix,
-                    const int64_t* file_offsets, int32_t files_per_frame, float* x, float* y,
-                    float* v, int32_t* gout, int32_t* pf, hipStream_t st, const uint32_t* entries,
-                    uint32_t* bnd = nullptr, bool* bnd_done = nullptr);
-int64_t polar_stage_words(int64_t n_files, int32_t rows);
-int32_t frame_times(const int32_t* pf, int64_t n, const int64_t* ids, float* t, hipStream_t st);
-int32_t sweep_to_points(const float* inten, const float* ranges, const float* cos_t,
-                        const float* sin_t, int32_t rows, int32_t bins, float thr,
-                        int32_t stride, float* x, float* y, float* z, int64_t capacity,
-                        int64_t* n_out_host, hipStream_t st);
-int32_t polar_to_cartesian(const float* cos_t, const float* sin_t, const float* ranges,
-                           int64_t rows, int64_t bins, float* x, float* y, hipStream_t st);
-int32_t infer_time_from_colors(const uint8_t* colors, int64_t n, const float* pal, int32_t n_pal,
-                               float* out, hipStream_t st);
-int32_t synth_echo(const rpt_synth_params* p, int64_t frame0, int64_t n_frames,
-                   const float* cos_t, const float* sin_t, const uint32_t* clutter_thresh,
-                   const float* targets, const int32_t* trows, const int32_t* tbins,
-                   uint8_t* echo, hipStream_t st);
 int32_t bounds_xy(const float* x, const float* y, int64_t n, float* out4, hipStream_t st);
 int32_t land_grid(const float* x, const float* y, const float* val, int64_t n, const double* xe,
                   int32_t nxe, const double* ye, int32_t nye, int32_t* cnt, double* tot,

@@ -1,7 +1,7 @@
 // Frame slots from frame offsets: the pure index logic of the stack driver's narrow path (no
 // per-point frame array).  off[0 .. F] are non-decreasing point offsets, off[0] = 0, off[F] = n;
 // point i belongs to the one frame f with off[f] <= i < off[f + 1] (empty frames repeat an
-// offset and own no point).  Shared by the kernels (land.hip, summaries.hip, polar.hip) and by
+// offset and own no point).  Shared by the kernels (land.hip, summaries.hip, polar_aux.inc) and by
 // the host check tools/asan/frame_index_main.cpp, so everything here is plain C++.
 #pragma once
 #include <cstdint>

@@ -1,6 +1,6 @@
 // Which kept samples of a 4-row group K1 emits, which of them the count pass stages and in which
 // layout: the pure arithmetic shared by the staged count pass, k_group_starts, k_file_staged and
-// k_group_write_u8 (polar.hip), and by the host check
+// k_group_write_u8 (polar_count.inc, polar_expand.inc, polar_write.inc), and by the host check
 // tools/asan/k1_emit_main.cpp, so everything here is plain C++.
 //
 // A file's kept samples are numbered in file order (the in-file rank); K1 emits those whose rank
@@ -22,9 +22,10 @@
 namespace rpt {
 
 // Words of the staging buffer per group.  In the by-rank layout a group has a slot of that many
-// words and is staged when it keeps 1 .. kStageSlots samples (polar.hip).  In the file-contiguous
-// layout (file-ordered count pass) a FILE has the gpf * kStageSlots words of its gpf groups as one
-// region that holds the file's emitted entries in output order, see emit_staged_file.
+// words and is staged when it keeps 1 .. kStageSlots samples (polar_count.inc).  In the
+// file-contiguous layout (file-ordered count pass) a FILE has the gpf * kStageSlots words of its
+// gpf groups as one region that holds the file's emitted entries in output order, see
+// emit_staged_file.
 constexpr int kStageSlots = 512;
 
 // stride >= 1; power-of-two strides (the reference's POINT_STRIDE = 4) divide by shifts
@@ -89,8 +90,8 @@ RPT_K1_HD uint32_t emit_staged_out(uint32_t so, const EmitSpan& s, uint32_t cap)
 // count and the write call.  The file-ordered count pass has whole files as its work units,
 // ceil(n_files / kCus) of them on the busiest CU; it is ahead of the by-rank pass when the busiest
 // CU has at most 1/19 more than the average, from the smallest stack it was measured ahead at
-// (the table is in polar.hip).  The file-contiguous entry holds the row within the FILE in 14
-// bits: taller sweeps take the by-rank layout.
+// (the table is in polar_count.inc).  The file-contiguous entry holds the row within the FILE in
+// 14 bits: taller sweeps take the by-rank layout.
 constexpr int64_t kCus = 256;  // MI355X
 constexpr int64_t kEmittedMinFiles = 1500;
 constexpr int kEntryRowBits = 14;

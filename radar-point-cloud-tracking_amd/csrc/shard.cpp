@@ -823,8 +823,7 @@ int32_t rpt_shard_polar(rpt_shard* h, const rpt_stack_params* p, const void* ech
   RPT_TRY(h->bnd.ensure((size_t)std::max<int64_t>(8, polar_bounds_words()), st));
   const size_t down_bytes = sizeof(int64_t) * (size_t)(n_files + 2) + 16;
   RPT_TRY(S.down.ensure(down_bytes, st));
-  const bool grouped = p->echo_dtype == RPT_ECHO_U8 && p->bins == 1024 &&
-                       (uintptr_t)echo % 16 == 0;
+  const bool grouped = polar_grouped_u8(echo, p->echo_dtype, p->bins);
   uint32_t* mk = nullptr;  // staged kept samples, as in rpt_stack_run
   if (grouped && ab().k1_stage) {
     RPT_TRY(S.k1_stage.ensure((size_t)polar_stage_words(n_files, p->rows), st));

@@ -137,8 +137,7 @@ int32_t rpt_stack::run(const rpt_stack_params& p, const void* echo, const float*
   // u8 sweeps of 1024 bins: the count pass stages the kept samples of every group that keeps at
   // most 128 of them (the sparse radar case) and the write pass reads those instead of the echo,
   // so K1 reads the echo once (ab().k1_stage off: two full reads)
-  const bool grouped = p.echo_dtype == RPT_ECHO_U8 && p.bins == 1024 &&
-                       (uintptr_t)echo % 16 == 0;
+  const bool grouped = polar_grouped_u8(echo, p.echo_dtype, p.bins);
   // the narrow point layout, on the same condition: no per-point frame slots (pf, pf2 stay
   // unallocated) -- the points are in frame order, so the land compaction, K9 and the hand-back
   // take a point's frame from the frame offsets (frame_index.h) -- and the intensities as the u8

@@ -11,28 +11,9 @@
 #include <vector>
 
 #include "common.h"
+#include "polar.h"  // K1 and the small kernels beside it
 
 namespace rpt {
-int32_t polar_count(const void* echo, int32_t dt, int64_t n_files, int32_t rows, int32_t bins,
-                    float thr, int32_t stride, int64_t* row_prefix, int64_t* file_offsets,
-                    int64_t* total_host, hipStream_t st, uint32_t* entries);
-int32_t polar_write_cap(const uint8_t* echo, int64_t n_files, int32_t rows, float thr,
-                        int32_t stride, const float* scale, const float* cos_t,
-                        const float* sin_t, const int32_t* gain, const int64_t* row_prefix,
-                        const int64_t* file_offsets, int32_t fpf, float* x, float* y, float* v,
-                        int32_t* gout, int32_t* pf, int64_t cap, hipStream_t st,
-                        const uint32_t* entries, uint32_t* bnd = nullptr,
-                        bool* bnd_done = nullptr);
-int32_t polar_write(const void* echo, int32_t dt, int64_t n_files, int32_t rows, int32_t bins,
-                    const float* scale, const float* cos_t, const float* sin_t,
-                    const int32_t* gain, float thr, int32_t stride, const int64_t* row_prefix,
-                    const int64_t* file_offsets, int32_t files_per_frame, float* x, float* y,
-                    float* v, int32_t* gout, int32_t* pf, hipStream_t st, const uint32_t* entries,
-                    uint32_t* bnd = nullptr, bool* bnd_done = nullptr);
-// words of polar_write's bnd buffer; the bounds it leaves in bnd[0..3] read back as floats
-int64_t polar_bounds_words();
-int64_t polar_stage_words(int64_t n_files, int32_t rows);
-int32_t frame_times(const int32_t* pf, int64_t n, const int64_t* ids, float* t, hipStream_t st);
 int32_t bounds_xy(const float* x, const float* y, int64_t n, float* out4, hipStream_t st);
 int32_t land_grid_cells(const float* x, const float* y, const float* val, int64_t n,
                         const double* xe, int32_t nxe, const double* ye, int32_t nye,
@@ -52,25 +33,6 @@ int32_t land_compact_dev(const float* x, const float* y, const float* v, const i
                          hipStream_t st, int64_t t_base = 0,
                          const int64_t* frame_off = nullptr, const uint16_t* cell16 = nullptr,
                          const uint8_t* v8 = nullptr, uint8_t* vo8 = nullptr);
-// the u8-intensity forms (u8 sweeps of 1024 bins, 16-B aligned rows): v holds the samples
-int32_t polar_write_cap(const uint8_t* echo, int64_t n_files, int32_t rows, float thr,
-                        int32_t stride, const float* scale, const float* cos_t,
-                        const float* sin_t, const int32_t* gain, const int64_t* row_prefix,
-                        const int64_t* file_offsets, int32_t fpf, float* x, float* y, uint8_t* v,
-                        int32_t* gout, int32_t* pf, int64_t cap, hipStream_t st,
-                        const uint32_t* entries, uint32_t* bnd = nullptr,
-                        bool* bnd_done = nullptr);
-int32_t polar_write(const uint8_t* echo, int64_t n_files, int32_t rows, const float* scale,
-                    const float* cos_t, const float* sin_t, const int32_t* gain, float thr,
-                    int32_t stride, const int64_t* row_prefix, const int64_t* file_offsets,
-                    int32_t fpf, float* x, float* y, uint8_t* v, int32_t* gout, int32_t* pf,
-                    hipStream_t st, const uint32_t* entries, uint32_t* bnd = nullptr,
-                    bool* bnd_done = nullptr);
-// out[i] = (float)in[i]
-int32_t bytes_to_float(const uint8_t* in, int64_t n, float* out, hipStream_t st);
-// t[i] = (float)f and pf[i] = f (each nullable) for the points [off[f], off[f + 1]) of every
-// frame f: frame slots from device frame offsets off[0 .. n_frames]
-int32_t frame_fill(const int64_t* off, int32_t n_frames, float* t, int32_t* pf, hipStream_t st);
 int32_t stdbscan(const float* x, const float* y, const float* z, int64_t stride, const float* t,
                  int64_t n, double eps_space, double eps_time, int32_t min_samples,
                  int32_t* labels, rpt_stdbscan_stats* stats, hipStream_t st, int dim);
@@ -83,8 +45,6 @@ size_t stdbscan_bounds_bytes();
 size_t stdbscan_bounds_part_bytes(int64_t n_max);
 int32_t stdbscan_bounds_dev(const float* x, const float* y, const float* t, int64_t n_max,
                             const int64_t* n_dev, void* out_dev, void* part_dev, hipStream_t st);
-int32_t frame_times_dev(const int32_t* pf, int64_t n_max, const int64_t* n_dev, float* t,
-                        hipStream_t st);
 int32_t stdbscan_fill_stats(void* state, int32_t n_clusters, rpt_stdbscan_stats* stats);
 int32_t stdbscan_core_flags(void* state, int64_t n, uint8_t* out, hipStream_t st);
 int32_t cluster_summaries_dev(const int32_t* labels, const float* x, const float* y,

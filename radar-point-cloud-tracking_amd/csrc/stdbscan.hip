@@ -44,6 +44,7 @@
 #include <vector>
 
 #include "common.h"
+#include "dispatch.h"  // with_bool, with_dim
 
 #pragma clang fp contract(off)
 
@@ -85,17 +86,6 @@ struct Timer {
       if (e) (void)hipEventDestroy(e);
   }
 };
-
-// A kernel form chosen at run time, its launch written once: f gets the template argument as an
-// std::integral_constant (f(std::true_type{}) / f(std::false_type{}); the grid's dimension 2 / 3).
-template <class F>
-auto with_bool(bool b, F&& f) {
-  return b ? f(std::true_type{}) : f(std::false_type{});
-}
-template <class F>
-auto with_dim(int dim, F&& f) {
-  return dim == 2 ? f(std::integral_constant<int, 2>{}) : f(std::integral_constant<int, 3>{});
-}
 
 }  // namespace
 

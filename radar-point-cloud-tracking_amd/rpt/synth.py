@@ -155,7 +155,7 @@ def _splitmix64(z: np.ndarray) -> np.ndarray:
 
 def numpy_echo(cfg: SynthConfig, geo: SynthGeometry, frames: Optional[range] = None
                ) -> np.ndarray:
-    """Bit-identical numpy restatement of k_synth (csrc/polar.hip) for local frames `frames`."""
+    """Bit-identical numpy restatement of k_synth (csrc/polar_aux.inc) for local frames `frames`."""
     frames = range(cfg.n_frames) if frames is None else frames
     G, R, B = len(cfg.gains), cfg.rows, cfg.bins
     out = np.zeros((len(frames), G, R, B), np.uint8)

@@ -1,7 +1,8 @@
-"""The staged K1 pair in its file-contiguous layout (csrc/polar.hip: k_group_count_u8_files stores
-a file's emitted entries as one dense array in output order, k_file_staged + k_expand_stream write
-them as a stream) against the two-full-read pair rpt_polar_count + rpt_polar_write: all six
-outputs by bit pattern, with NaN / -1 sentinels in the output arrays.
+"""The staged K1 pair in its file-contiguous layout (csrc/polar_count.inc: k_group_count_u8_files
+stores a file's emitted entries as one dense array in output order; csrc/polar_expand.inc:
+k_file_staged + k_expand_stream write them as a stream) against the two-full-read pair
+rpt_polar_count + rpt_polar_write: all six outputs by bit pattern, with NaN / -1 sentinels in the
+output arrays.
 
 File f owns C = ceil(rows / 4) * 512 words of the staging buffer; a group that emits the file's
 outputs [first, first + m) is staged iff m != 0 and first + m <= C (k1_emit.h emit_staged_file),

@@ -3,7 +3,8 @@ file's groups are counted in file order by one workgroup of W waves, and only th
 write pass emits are staged -- against the two-full-read pair rpt_polar_count + rpt_polar_write,
 which golden vector g1 pins to the reference.  All six outputs must be equal exactly.
 
-The layout and W follow from n_files alone (polar.hip staged_emitted, count_waves_per_file):
+The layout and W follow from n_files alone (k1_emit.h staged_emitted, polar_count.inc
+count_waves_per_file):
 
     emitted layout   n_files >= 1500 and 20 * n_files >= 19 * 256 * ceil(n_files / 256)
                      (the busiest of the 256 CUs has at most 1/19 more files than the average)
