@@ -110,6 +110,10 @@ struct DbscanState {
   bool cmin_ready = false;  // cell_min_pair filled by the core pass for the current core flags
   void* crec = nullptr;                      // CellRec<dim>[C + 1]
   uint32_t* occ_bits = nullptr;              // 1 bit per cell
+  // per-cell path (cell_comp): 1 bit per cell with a core point (rep[c] >= 0), every word written
+  // by k_parent_init_cells, and its dilation over the label pass's window reach (integral times;
+  // k_near_bits, every word written per run).  Laid out and padded as occ_bits.
+  uint32_t *core_bits = nullptr, *near_bits = nullptr;
   uint4* pmask = nullptr;  // union passes' undecided-candidate masks per occupied cell (aliases
                            // the grid build's radix key buffers, dead after the build)
   // occupied cells per wave iteration of k_union_cells_pair: 64 on large stacks (one header load
@@ -179,6 +183,18 @@ struct DbscanState {
     return all_mutual && dim == 2 && a.union_list && a.union_pair && a.union_nm && a.cell_comp &&
            !use_label_tiles() && !a.uf_compress;
   }
+  // ... and its label stage takes k_label's candidates from core_bits: every k_label form a
+  // cell_comp run can launch (32 or 64 lanes, float4 or xy points) then reads cell_min only where
+  // core_bits is set, as k_label_core_cells does for core points (the label tiles rule cell_comp
+  // out).  Needs the exact slab windows of integral times (an infinite eps_time has g.rt = -1).
+  bool core_bits_ok() const { return cell_comp_ok() && g.rt >= 0; }
+  // ... and near_bits is built and tested per non-core point in k_label_core_cells, and cell_min
+  // gets no INT_MAX fill (no reader looks at a cell without core points then, see above).  Not on
+  // dense slabs, where nearly every point is core and the queue is a few thousand points
+  // (configs[4] share: k_label 4.8 us, against +10.7 us for k_near_bits and +23.6 us in
+  // k_label_core_cells<true>); there the label stage keeps the fill as well, so its kernels run
+  // as before.
+  bool near_bits_ok() const { return core_bits_ok() && !dense_slabs; }
   // The sorted points are float2 {x, y} in the first half of pts' allocation (Pt<true>), not
   // float4: the build's writer was k_slab_bucket<true> / k_slab_chunk_scatter<true>.  A kernel
   // that assumed the other layout would read out of bounds, so the one rule is xy_rule() and
@@ -365,6 +381,8 @@ int32_t DbscanState::build_t(const float* x, const float* y, const float* z, int
   bud.add<int32_t>(n + 1);  // hpos
   bud.add<CellRec<D>>(C1);  // crec
   bud.add<uint32_t>(C1 / 32 + 2);  // occupancy bits
+  bud.add<uint32_t>(C1 / 32 + 2);  // core_bits
+  bud.add<uint32_t>(C1 / 32 + 2);  // near_bits
   bud.add<int32_t>(nt + 1);        // slab_lo (slab-bucket path)
   bud.add<int32_t>(nt + 1);        // slab_occ (slab-bucket path)
   bud.add<int32_t>(nt + 1);        // occ_base (slab-bucket path)
@@ -403,6 +421,8 @@ int32_t DbscanState::build_t(const float* x, const float* y, const float* z, int
   CellRec<D>* cr = arena.carve_n<CellRec<D>>(C1);
   crec = cr;
   occ_bits = arena.carve_n<uint32_t>(C1 / 32 + 2);  // +1: two-word window reads
+  core_bits = arena.carve_n<uint32_t>(C1 / 32 + 2);
+  near_bits = arena.carve_n<uint32_t>(C1 / 32 + 2);
   int32_t* slab_lo = arena.carve_n<int32_t>(nt + 1);
   int32_t* slab_occ = arena.carve_n<int32_t>(nt + 1);
   int32_t* occ_base = arena.carve_n<int32_t>(nt + 1);
@@ -789,18 +809,24 @@ int32_t DbscanState::union_pass(hipStream_t st, bool fused) {
     hipLaunchKernelGGL(k_cell_min_pair, dim3(gb), dim3(kBlock), 0, st, skey, core, sorig, n, C,
                        cmin);
   if (cell_comp)
-    hipLaunchKernelGGL(k_parent_init_cells, dim3(gb), dim3(kBlock), 0, st, occ, n_occ, C, cmin,
-                       rep, parent, pcount, nm_count, min_bits, min_words(), cell_min);
+    hipLaunchKernelGGL(k_parent_init_cells, dim3(gb), dim3(kBlock), 0, st, C, cmin, rep, parent,
+                       pcount, nm_count, min_bits, min_words(),
+                       near_bits_ok() ? (int32_t*)nullptr : cell_min, occ_bits, core_bits,
+                       (int64_t)((C + 1) / 32 + 2));
   else
     hipLaunchKernelGGL(k_parent_init_pair, dim3(grid_for(n, kBlock * kPU, 2048)), dim3(kBlock), 0,
                        st, parent, n, core, skey, mutual, cmin, C, rep);
   int32_t* lstat_dev = nullptr;  // (A/B diagnostics)
   if (dim == 2) {
     uint4* pm = listing ? pmask : nullptr;
-    if (a.union_pair)  // two cells per wave (RPT_UNION_PAIR=0 in the A/B build: one)
-      hipLaunchKernelGGL(k_union_cells_pair, dim3(gw), dim3(kBlock), 0, st, pts, g, occ, n_occ,
-                         rec<2>(), occ_bits, slab_t, rep, mutual, sorig, parent, uf_flags, pm,
-                         plist, pcount, union_cpw(), nm_list, nm_count);
+    if (a.union_pair && cell_comp)  // candidates by core_bits, no mutual[] per candidate
+      hipLaunchKernelGGL(k_union_cells_pair<true>, dim3(gw), dim3(kBlock), 0, st, pts, g, occ,
+                         n_occ, rec<2>(), core_bits, slab_t, rep, mutual, sorig, parent, uf_flags,
+                         pm, plist, pcount, union_cpw(), nm_list, nm_count);
+    else if (a.union_pair)  // two cells per wave (RPT_UNION_PAIR=0 in the A/B build: one)
+      hipLaunchKernelGGL(k_union_cells_pair<false>, dim3(gw), dim3(kBlock), 0, st, pts, g, occ,
+                         n_occ, rec<2>(), occ_bits, slab_t, rep, mutual, sorig, parent, uf_flags,
+                         pm, plist, pcount, union_cpw(), nm_list, nm_count);
     else
       hipLaunchKernelGGL((k_union_cells<2, false>), dim3(gw), dim3(kBlock), 0, st, pts, g,
                          cell_start, occ, n_occ, rec<2>(), occ_bits, slab_t, core, rep, mutual,
@@ -922,11 +948,19 @@ int32_t DbscanState::labels_local(int32_t* labels, rpt_stdbscan_stats* stats, hi
   int32_t* nc_count = nc_list + n;
   const MinRank mr{min_bits, min_pref};
   const unsigned glc = (unsigned)((grid_for(n, kBlock * kPU, 2048) + 7) & ~7);
+  // the per-cell path by the core-cell bitmaps (core_bits written by k_parent_init_cells)
+  const bool bits = cell_comp && core_bits_ok();
+  const bool nearb = cell_comp && near_bits_ok();
   if (cell_comp) {
     // component ids per occupied cell (minimum bits and cell_min = INT_MAX cleared by
     // k_parent_init_cells), the rank prefix, then core labels + the non-core queue in one
     // per-point pass; ccmin is not written.  cid[n]: the union pass's non-mutual-cell count
     const int64_t W = min_words();
+    if (nearb) {
+      const int nbw = (int)((C + 1) / 32 + 2);
+      hipLaunchKernelGGL(k_near_bits, dim3(grid_for(nbw, kBlock, 2048)), dim3(kBlock), 0, st,
+                         core_bits, nbw, g.nx, g.ny, g.rt, near_bits);
+    }
     hipLaunchKernelGGL(k_cell_comp, dim3(grid_for(n, kBlock, 2048)), dim3(kBlock), 0, st, parent,
                        occ, n_occ_dev, C, rep, sorig, cell_min, min_bits, nc_count);
     hipLaunchKernelGGL(k_word_popc, dim3(grid_for(W, kBlock, 2048)), dim3(kBlock), 0, st,
@@ -934,9 +968,12 @@ int32_t DbscanState::labels_local(int32_t* labels, rpt_stdbscan_stats* stats, hi
     RPT_CHECK_LAUNCH();
     RPT_TRY(exclusive_scan_total_i32(min_pref, min_pref, W, st));
     with_bool(spos_on, [&](auto orig) {  // (ORIG: perm = spos, else sorig)
-      hipLaunchKernelGGL(k_label_core_cells<orig.value>, dim3(glc), dim3(kBlock), 0, st, skey,
-                         core, orig.value ? slab : sorig, n, C, cell_min, mr, labels, nc_list,
-                         nc_count, cid + n, n_clusters_ptr());
+      with_bool(nearb, [&](auto nr) {
+        hipLaunchKernelGGL((k_label_core_cells<orig.value, nr.value>), dim3(glc), dim3(kBlock), 0,
+                           st, skey, core, orig.value ? slab : sorig, n, C, cell_min, mr, labels,
+                           nc_list, nc_count, cid + n, n_clusters_ptr(),
+                           nr.value ? (const uint32_t*)near_bits : nullptr);
+      });
     });
   } else {
     // also the per-cell smallest keys (k_cell_min_key fused; cell_min filled with INT_MAX by
@@ -966,25 +1003,30 @@ int32_t DbscanState::labels_local(int32_t* labels, rpt_stdbscan_stats* stats, hi
                        n_occ_dev, rowq, rec<2>(), mutual, occ_bits, slab_t, pts, ccmin, cell_min,
                        sorig, mr, min_samples, labels);
   else if (cell_comp && ab().k7_w == 64)
-    hipLaunchKernelGGL((k_label<2, false, 64, true>), dim3(wave_grid(n)), dim3(kBlock), 0, st,
-                       pts, skey, g, rec<2>(), occ_bits, slab_t, (const int32_t*)nullptr,
-                       cell_min, mutual, sorig, mr, nc_list, nc_count, labels,
-                       (int32_t*)nullptr, core);
+    with_bool(bits, [&](auto b) {
+      hipLaunchKernelGGL((k_label<2, false, 64, true, false, b.value>), dim3(wave_grid(n)),
+                         dim3(kBlock), 0, st, pts, skey, g, rec<2>(), occ_bits, slab_t,
+                         (const int32_t*)nullptr, cell_min, mutual, sorig, mr, nc_list, nc_count,
+                         labels, (int32_t*)nullptr, core, core_bits);
+    });
   else if (dim == 2 && ab().k7_w == 64)
     hipLaunchKernelGGL((k_label<2, false, 64>), dim3(wave_grid(n)), dim3(kBlock), 0, st, pts,
                        skey, g, rec<2>(), occ_bits, slab_t, ccmin, cell_min, mutual, sorig, mr,
                        nc_list, nc_count, labels);
   else
 #endif
-  if (cell_comp && xy_points)
-    hipLaunchKernelGGL((k_label<2, false, 32, true, true>), dim3(wave_grid(n)), dim3(kBlock), 0,
-                       st, reinterpret_cast<const Pt<true>*>(pts), skey, g, rec<2>(), occ_bits,
-                       slab_t, (const int32_t*)nullptr, cell_min, mutual, sorig, mr, nc_list,
-                       nc_count, labels, kstat, core);
+  if (cell_comp && xy_points)  // (xy_rule: integral eps_t windows, so bits)
+    hipLaunchKernelGGL((k_label<2, false, 32, true, true, true>), dim3(wave_grid(n)),
+                       dim3(kBlock), 0, st, reinterpret_cast<const Pt<true>*>(pts), skey, g,
+                       rec<2>(), occ_bits, slab_t, (const int32_t*)nullptr, cell_min, mutual,
+                       sorig, mr, nc_list, nc_count, labels, kstat, core, core_bits);
   else if (cell_comp)
-    hipLaunchKernelGGL((k_label<2, false, 32, true>), dim3(wave_grid(n)), dim3(kBlock), 0, st,
-                       pts, skey, g, rec<2>(), occ_bits, slab_t, (const int32_t*)nullptr,
-                       cell_min, mutual, sorig, mr, nc_list, nc_count, labels, kstat, core);
+    with_bool(bits, [&](auto b) {
+      hipLaunchKernelGGL((k_label<2, false, 32, true, false, b.value>), dim3(wave_grid(n)),
+                         dim3(kBlock), 0, st, pts, skey, g, rec<2>(), occ_bits, slab_t,
+                         (const int32_t*)nullptr, cell_min, mutual, sorig, mr, nc_list, nc_count,
+                         labels, kstat, core, core_bits);
+    });
   else if (dim == 2)
     hipLaunchKernelGGL((k_label<2, false, 32>),
                        dim3(wave_grid(n)), dim3(kBlock), 0, st, pts, skey, g,

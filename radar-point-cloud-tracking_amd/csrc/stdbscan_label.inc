@@ -9,7 +9,8 @@
 // (uf_*).  The A/B-only forms (stdbscan_ab.inc) are included after k_label.
 // Cluster id = rank of the component minimum among all minima (MinRank); core: own id; non-core:
 // min id over adjacent core points, else -1.
-//   local, per-cell path (cell_comp): k_cell_comp, k_word_popc, scan, k_label_core_cells
+//   local, per-cell path (cell_comp): k_cell_comp, k_word_popc, scan, k_near_bits (near_bits from
+//     K6's core_bits, DbscanState::near_bits_ok), k_label_core_cells
 //   local, otherwise: k_cell_roots, k_ccmin, k_word_popc, scan, k_label_core(_orig)
 //   then k_label over the queued non-core points
 //   global: k_cell_roots, k_ccmin_global, k_label_global_orig, k_label_global_core, k_label
@@ -289,6 +290,39 @@ __global__ __launch_bounds__(kBlock) void k_cell_comp(int32_t* parent,
   }
 }
 
+// near_bits = core_bits dilated over the label pass's window (+-2 cells in x and y, +-rt slabs:
+// slab_window's reach): one thread per word, every word written.  The key is (slab * ny + y) * nx
+// + x, so a neighbour at (dx, dy, ds) is the bit at + (ds * ny + dy) * nx + dx: per (ds, dy) the
+// three words around the shifted position give the five x shifts.  A shift that runs over a row or slab end only sets bits (the point is queued and finds no core cell); no
+// true neighbour is lost, and words outside the array read as zero.  The bitmap stays in L2
+// (0.86 MB at 1000 frames).
+__global__ __launch_bounds__(kBlock) void k_near_bits(const uint32_t* __restrict__ core_bits,
+                                                     int nbw, int nx, int ny, int rt,
+                                                     uint32_t* __restrict__ near_bits) {
+  // (the pass is VALU per word: 32-bit word indices -- the grid holds at most 2^30 cells -- and
+  // one variable shift per row)
+  auto word = [&](int k) -> uint32_t {  // branch-free: clamped index, result masked
+    const uint32_t v = core_bits[min(max(k, 0), nbw - 1)];
+    return (k >= 0 && k < nbw) ? v : 0u;
+  };
+  for (int w = blockIdx.x * blockDim.x + threadIdx.x; w < nbw; w += gridDim.x * blockDim.x) {
+    uint32_t acc = 0;
+    for (int ds = -rt; ds <= rt; ++ds) {
+#pragma unroll
+      for (int dy = -2; dy <= 2; ++dy) {
+        // x = bits [p, p + 36) of the string: the row's cells x - 2 .. x + 2 of this word's 32
+        const int64_t p = (int64_t)w * 32 + ((int64_t)ds * ny + dy) * nx - 2;
+        const int k = (int)(p >> 5), sh = (int)(p & 31);  // (arithmetic shift: floor)
+        const uint32_t a = word(k), b = word(k + 1), c = word(k + 2);
+        uint64_t x = (((uint64_t)b << 32) | a) >> sh;
+        x |= sh ? ((uint64_t)c << (64 - sh)) : 0ull;
+        acc |= (uint32_t)(x | (x >> 1) | (x >> 2) | (x >> 3) | (x >> 4));
+      }
+    }
+    near_bits[w] = acc;
+  }
+}
+
 // K7/K8 (core points) on all_mutual grids, with the non-core queue folded in: a core point's
 // label is the rank of its CELL's component minimum (cell_key[skey[s]]; sorted points are runs of
 // equal keys, so the lookup is a broadcast load), a non-core point is queued for k_label.
@@ -300,17 +334,23 @@ __global__ __launch_bounds__(kBlock) void k_cell_comp(int32_t* parent,
 // guard: the box-certain union pass's count of non-mutual cells with core points.  all_mutual
 // promises zero; if it is not, the labels are not valid and the cluster count (written by the
 // scan before this kernel) is replaced by -1, which fails the call at the readback of the count.
+// NEAR (near = k_near_bits' bitmap; null otherwise): a non-core point whose cell's bit is clear has no cell with a core
+// point anywhere in its window, so its label is -1, written here, and it is not queued (on the
+// radar stacks 43-46 % of the non-core points).  The word is loaded with cell_key[k], for the
+// non-core points only: both depend on the key, so no level is added.  The isolated cell's points
+// (key >= cells) stay queued.
 struct AppendSpos {
   const int32_t* spos;
   __device__ int32_t operator()(int64_t i) const { return spos[i]; }
 };
-template <bool ORIG>
+template <bool ORIG, bool NEAR>
 __global__ __launch_bounds__(kBlock) void k_label_core_cells(
     const int32_t* __restrict__ skey, const uint8_t* __restrict__ core,
     const int32_t* __restrict__ perm, int64_t n, int64_t cells,
     const int32_t* __restrict__ cell_key, MinRank cid, int32_t* __restrict__ labels,
     int32_t* __restrict__ nc_list, int32_t* __restrict__ nc_count,
-    const int32_t* __restrict__ guard, int32_t* __restrict__ n_clusters) {
+    const int32_t* __restrict__ guard, int32_t* __restrict__ n_clusters,
+    const uint32_t* __restrict__ near) {
   if (blockIdx.x == 0 && threadIdx.x == 0 && *guard != 0) *n_clusters = -1;
   const int64_t T = (n + (int64_t)kBlock * kPU - 1) / ((int64_t)kBlock * kPU);
   const bool xm = (gridDim.x & 7) == 0;
@@ -341,7 +381,14 @@ __global__ __launch_bounds__(kBlock) void k_label_core_cells(
       }
     }
     int32_t own[kPU];
-    uint32_t inb = 0, cb = 0;
+    uint32_t inb = 0, cb = 0, far = 0;
+    uint32_t nw[kPU];
+#pragma unroll
+    for (int u = 0; u < kPU; ++u) {  // (non-core points only: a few per cent; no wait in here)
+      const bool in = tile + (int64_t)u * kBlock + threadIdx.x < n;
+      nw[u] = ~0u;
+      if (NEAR && in && c[u] == 0u && k[u] >= 0 && (int64_t)k[u] < cells) nw[u] = near[k[u] >> 5];
+    }
 #pragma unroll
     for (int u = 0; u < kPU; ++u) {
       const bool in = tile + (int64_t)u * kBlock + threadIdx.x < n;
@@ -350,6 +397,10 @@ __global__ __launch_bounds__(kBlock) void k_label_core_cells(
       cb |= (in && c[u] != 0u) ? (1u << u) : 0u;
       const int32_t v = cell_key[q ? k[u] : 0];  // cells >= 1
       own[u] = (q && v != INT_MAX) ? v : -1;
+    }
+    if (NEAR) {
+#pragma unroll
+      for (int u = 0; u < kPU; ++u) far |= ((nw[u] >> (k[u] & 31)) & 1u) ? 0u : (1u << u);
     }
     uint32_t w[kPU];
     int32_t pr[kPU];
@@ -367,13 +418,33 @@ __global__ __launch_bounds__(kBlock) void k_label_core_cells(
           labels[tile + (int64_t)u * kBlock + threadIdx.x] = lab;
         else
           labels[pv[u]] = lab;
+      } else if ((far >> u) & 1u) {
+        if (ORIG)
+          labels[tile + (int64_t)u * kBlock + threadIdx.x] = -1;
+        else
+          labels[pv[u]] = -1;
       }
     }
     if (ORIG)
-      block_append_bits(tile, inb & ~cb, nc_list, nc_count, AppendSpos{perm});
+      block_append_bits(tile, inb & ~cb & ~far, nc_list, nc_count, AppendSpos{perm});
     else
-      block_append_bits(tile, inb & ~cb, nc_list, nc_count);
+      block_append_bits(tile, inb & ~cb & ~far, nc_list, nc_count);
   }
+}
+
+// position of the n-th set bit of m (n < popcount(m)): halving by popcounts
+__device__ __forceinline__ int nth_set_bit(uint64_t m, int n) {
+  int pos = 0;
+#pragma unroll
+  for (int s = 32; s > 0; s >>= 1) {
+    const int c = __popcll(m & ((1ull << s) - 1ull));
+    if (n >= c) {
+      n -= c;
+      m >>= s;
+      pos += s;
+    }
+  }
+  return pos;
 }
 
 // K7/K8 (non-core points, queued): the smallest component key over adjacent core points, else
@@ -389,7 +460,9 @@ __global__ __launch_bounds__(kBlock) void k_label_core_cells(
 //                 (ccmin) is not written -- the core flag core_of[j] stands for key_of[j] >= 0, the
 //                 non-mutual search and the mutual[] loads compile out.
 // XY: float2 points (ALLMUT grids only); the window comes from the key's slab.
-template <int D, bool GLOBAL, int W = 64, bool ALLMUT = false, bool XY = false>
+// BITS (ALLMUT grids with integral-time windows, g.rt >= 0): the candidates are the set bits of
+//                 core_bits in the window instead of a cell_key gather over all of it (below).
+template <int D, bool GLOBAL, int W = 64, bool ALLMUT = false, bool XY = false, bool BITS = false>
 // 6 waves/SIMD (80 VGPRs, no spill; with two candidate points per lane per round 7 spilled 8)
 // W = 32: two points per wave, one per half (the same candidate loads per point, twice the
 // points in flight: the pass is a chain of dependent loads per point, not bandwidth)
@@ -407,8 +480,10 @@ __global__ __launch_bounds__(kBlock, 6) void k_label(const Pt<XY>* __restrict__ 
                                                  const int32_t* __restrict__ nc_count,
                                                  int32_t* __restrict__ labels,
                                                  int32_t* __restrict__ kstat = nullptr,
-                                                 const uint8_t* __restrict__ core_of = nullptr) {
+                                                 const uint8_t* __restrict__ core_of = nullptr,
+                                                 const uint32_t* __restrict__ core_bits = nullptr) {
   static_assert(!ALLMUT || (D == 2 && !GLOBAL), "all-mutual grids are 2-D, local runs");
+  static_assert(!BITS || ALLMUT, "core_bits is built on the per-cell path of all-mutual grids");
   static_assert(!XY || ALLMUT, "xy points only on all-mutual grids");
   // kstat (A/B build, RPT_STATS): queued points, points with a core cell in their window, points
   // that searched a partly reachable cell, points labelled
@@ -450,19 +525,69 @@ __global__ __launch_bounds__(kBlock, 6) void k_label(const Pt<XY>* __restrict__ 
       // super-rounds of kR candidates per lane, loads of one kind issued together: the cells'
       // smallest keys (empty cells hold INT_MAX, so no occupancy lookup), then the records of
       // the cells with core points -- two dependent rounds per super-round
-      for (int base = 0; base < w.total; base += W * kR) {
-        int64_t c[kR];
-        int ck[kR], cb[kR], ce[kR], cls[kR], mu[kR];
+      // BITS: the window's cells with core points come from core_bits first.  Each lane takes one
+      // (slab, row) of the window (5 nS of them, W at a time) and reads the row's 5-bit field by a
+      // two-word read; the five ballots of the field's bits are the set positions of this chunk
+      // of rows, and the lanes take them one each (position idx = the idx-th set bit, x-major).
+      // cell_key and the records are then loaded for cells with core points only (8-9 of the 75
+      // on the radar stacks: one round), and cell_key needs no INT_MAX in the other cells.
+      constexpr int NK = BITS ? 1 : kR;  // candidates per lane per super-round
+      const int nrows = BITS ? 5 * w.nS : 1;
+      for (int rbase = 0; rbase < nrows; rbase += W) {  // (one pass unless BITS; body not indented)
+      uint64_t bx[5] = {0, 0, 0, 0, 0};
+      int tot = w.total;
+      if (BITS) {
+        const int row = rbase + hl;
+        const int ss = row / 5, yy = row - ss * 5;
+        const int y = w.y0 + yy;
+        uint32_t f = 0;
+        if (row < nrows && y >= 0 && y < g.ny) {
+          const int xlo = max(w.x0, 0), xhi = min(w.x0 + 4, g.nx - 1);  // (cx is in the grid)
+          const int64_t pb = ((int64_t)(w.s0 + ss) * g.ny + y) * g.nx + xlo;
+          const uint64_t two = ((uint64_t)core_bits[(pb >> 5) + 1] << 32) | core_bits[pb >> 5];
+          f = ((uint32_t)(two >> (pb & 31)) & ((1u << (xhi - xlo + 1)) - 1u)) << (xlo - w.x0);
+        }
+        tot = 0;
 #pragma unroll
-        for (int k = 0; k < kR; ++k) {
-          const int qq = base + k * W + hl;
-          c[k] = (qq < w.total) ? window_cell<D>(w, qq, g, slab_t, p.w, p.w) : -1;
+        for (int xx = 0; xx < 5; ++xx) {
+          bx[xx] = gbal((f >> xx) & 1u);
+          tot += __popcll(bx[xx]);
+        }
+      }
+      for (int base = 0; base < tot; base += W * NK) {
+        int64_t c[NK];
+        int ck[NK], cb[NK], ce[NK], cls[NK], mu[NK];
+        if (BITS) {
+          int idx = base + hl, qq = -1;
+          if (idx < tot) {
+            uint64_t m = 0;
+            int xs = 0;
+            bool found = false;
+#pragma unroll
+            for (int xx = 0; xx < 5; ++xx) {
+              const int cn = __popcll(bx[xx]);
+              if (!found && idx < cn) {
+                m = bx[xx];
+                xs = xx;
+                found = true;
+              }
+              if (!found) idx -= cn;
+            }
+            qq = (rbase + nth_set_bit(m, idx)) * 5 + xs;
+          }
+          c[0] = (qq >= 0) ? window_cell<D>(w, qq, g, slab_t, p.w, p.w) : -1;
+        } else {
+#pragma unroll
+          for (int k = 0; k < NK; ++k) {
+            const int qq = base + k * W + hl;
+            c[k] = (qq < w.total) ? window_cell<D>(w, qq, g, slab_t, p.w, p.w) : -1;
+          }
         }
 #pragma unroll
-        for (int k = 0; k < kR; ++k) ck[k] = (c[k] >= 0) ? cell_key[c[k]] : INT_MAX;
+        for (int k = 0; k < NK; ++k) ck[k] = (c[k] >= 0) ? cell_key[c[k]] : INT_MAX;
         int v = INT_MAX;
 #pragma unroll
-        for (int k = 0; k < kR; ++k) {
+        for (int k = 0; k < NK; ++k) {
           cb[k] = ce[k] = cls[k] = mu[k] = 0;
           if (ck[k] != INT_MAX) {
             const CellRec<D> cr = crec[c[k]];
@@ -478,18 +603,18 @@ __global__ __launch_bounds__(kBlock, 6) void k_label(const Pt<XY>* __restrict__ 
         {
           bool anyc = false;
 #pragma unroll
-          for (int k = 0; k < kR; ++k) anyc = anyc || ck[k] != INT_MAX;
+          for (int k = 0; k < NK; ++k) anyc = anyc || ck[k] != INT_MAX;
           st_core = st_core || gbal(anyc) != 0;
         }
 #endif
         // the partially reachable cells, smallest key first, while a key can still win
         uint32_t pend = 0;
 #pragma unroll
-        for (int k = 0; k < kR; ++k) pend |= (cls[k] == 2) ? (1u << k) : 0u;
+        for (int k = 0; k < NK; ++k) pend |= (cls[k] == 2) ? (1u << k) : 0u;
         while (true) {
           int mine = INT_MAX, mk = -1;
 #pragma unroll
-          for (int k = 0; k < kR; ++k)
+          for (int k = 0; k < NK; ++k)
             if (((pend >> k) & 1u) && ck[k] < best && ck[k] < mine) {
               mine = ck[k];
               mk = k;
@@ -504,7 +629,7 @@ __global__ __launch_bounds__(kBlock, 6) void k_label(const Pt<XY>* __restrict__ 
           const int kl = __shfl(mk, l);
           int bsel = 0, esel = 0, msel = 0;
 #pragma unroll
-          for (int k = 0; k < kR; ++k)
+          for (int k = 0; k < NK; ++k)
             if (k == kl) {
               bsel = cb[k];
               esel = ce[k];
@@ -547,6 +672,7 @@ __global__ __launch_bounds__(kBlock, 6) void k_label(const Pt<XY>* __restrict__ 
             best = min(best, gmin(lb));
           }
         }
+      }
       }
     }
     if (hl == 0) {

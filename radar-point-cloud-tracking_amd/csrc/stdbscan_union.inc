@@ -6,7 +6,9 @@
 // slab_t, the sorted points and, where the core pass left them (cmin_ready), the cells' minima.
 // Leaves behind parent (every root its component's minimum original index), rep (per cell: its
 // representative, the core point with the smallest original index) and cell_min_pair; the
-// per-cell init (cell_comp) also clears min_bits and fills cell_min for the label stage.  Its
+// per-cell init (cell_comp) also clears min_bits, writes core_bits (one bit per cell with a core
+// point; k_union_cells_pair<true>'s candidate filter, then the label stage's) and, where the
+// label stage needs it, fills cell_min.  Its
 // scratch is free until the label stage: the listed cells in nc_list (count at nc_list[n]) with
 // their masks in pmask, the non-mutual cells in cid (count at cid[n]), the root snapshot in
 // cell_root.
@@ -117,17 +119,24 @@ __global__ __launch_bounds__(kBlock) void k_parent_init_pair(
 // The star initialisation per CELL, for grids on which every occupied cell is mutual
 // (DbscanState::all_mutual): a cell's core points are one component, so the union passes and the
 // per-cell component pass (k_cell_comp) only ever read parent[] of cell representatives -- the
-// other points' entries are not written at all.  One thread per occupied cell: rep[c] = the
-// sorted index of the cell's minimum-original-index core point (-1: no core point), which is
-// its own root.  Folded in: the union passes' list counters (as k_init_occ_cells), and the label
-// stage's clears that k_cell_roots carries on the generic path (minimum bits, cell_key = INT_MAX
-// for all cells; both first written by k_cell_comp).
+// other points' entries are not written at all.  rep[c] = the sorted index of the cell's
+// minimum-original-index core point (-1: no core point), which is its own root.  Folded in: the
+// union passes' list counters (as k_init_occ_cells), and the label stage's clears that
+// k_cell_roots carries on the generic path (minimum bits, cell_key = INT_MAX for all cells; both
+// first written by k_cell_comp).
+// One loop over the DENSE cells, a wave per 64 consecutive cells: each lane takes its cell's
+// occupancy bit (occ_bits lists the same cells as occ) and, where set, its minimum pair, and the
+// ballot of rep >= 0 is two whole words of core_bits -- one bit per cell, set iff the cell holds
+// a core point.  All nbw words (occ_bits' padded count) are written every run, with no clear and
+// no atomic.
+// cell_key (nullable): filled with INT_MAX.  Null where every reader of the run looks only at
+// cells with a core point, which k_cell_comp writes (DbscanState::core_bits_ok).
 __global__ __launch_bounds__(kBlock) void k_parent_init_cells(
-    const int32_t* __restrict__ occ, const int32_t* __restrict__ n_occ, int64_t cells,
-    const unsigned long long* __restrict__ cmin, int32_t* __restrict__ rep,
+    int64_t cells, const unsigned long long* __restrict__ cmin, int32_t* __restrict__ rep,
     int32_t* __restrict__ parent, int32_t* __restrict__ zero_counter,
     int32_t* __restrict__ zero_counter2, uint32_t* __restrict__ zwords, int64_t nzw,
-    int32_t* __restrict__ cell_key) {
+    int32_t* __restrict__ cell_key, const uint32_t* __restrict__ occ_bits,
+    uint32_t* __restrict__ core_bits, int64_t nbw) {
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     if (zero_counter) *zero_counter = 0;
     if (zero_counter2) *zero_counter2 = 0;
@@ -135,15 +144,23 @@ __global__ __launch_bounds__(kBlock) void k_parent_init_cells(
   const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t ts = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = t0; i < nzw; i += ts) zwords[i] = 0u;
-  for (int64_t i = t0; i < cells; i += ts) cell_key[i] = INT_MAX;
-  const int64_t m = *n_occ;
-  for (int64_t q = t0; q < m; q += ts) {
-    const int32_t c = occ[q];
-    if ((int64_t)c >= cells) continue;
-    const unsigned long long v = cmin[c];
-    const int32_t r = (v != ~0ull) ? (int32_t)(uint32_t)v : -1;
-    rep[c] = r;
-    if (r >= 0) parent[r] = r;
+  const int lane = threadIdx.x & 63;
+  // (wave-uniform trip count: i - lane is the wave's first cell, a multiple of 64)
+  for (int64_t i = t0; i - lane < nbw * 32; i += ts) {
+    const bool in = i < cells;  // (the isolated cell, past them, has no entry)
+    const bool o = in && ((occ_bits[i >> 5] >> (i & 31)) & 1u);
+    int32_t r = -1;
+    if (o) {
+      const unsigned long long v = cmin[i];
+      r = (v != ~0ull) ? (int32_t)(uint32_t)v : -1;
+      rep[i] = r;
+      if (r >= 0) parent[r] = r;
+    }
+    const uint64_t b = __ballot(r >= 0);
+    const int64_t w = (i - lane) >> 5;
+    if (lane == 0) core_bits[w] = (uint32_t)b;
+    if (lane == 32 && w + 1 < nbw) core_bits[w + 1] = (uint32_t)(b >> 32);
+    if (cell_key && in) cell_key[i] = INT_MAX;
   }
 }
 
@@ -442,7 +459,11 @@ __device__ __forceinline__ bool block_last_wave(int* done, int lane) {
 // cells' dependent load chains (record -> occupancy -> candidate records -> roots) are in flight
 // per wave instead of one.  Same unions, undecided-candidate masks (position p -> bit p of the
 // 128-bit pmask, as k_union_listed reads them) and plist as k_union_cells<2, false>.
+// CORE (the per-cell path of all-mutual grids): occ_bits is core_bits, so a candidate without a
+// core point costs no record and no rep load (a fifth of the occupied forward candidates of a core
+// cell on the radar stacks), and no candidate's mutual[] is loaded (every one is mutual).
 // 6 waves/SIMD (77 VGPRs, no spill; the unconstrained build took 81 and 5)
+template <bool CORE>
 __global__ __launch_bounds__(kBlock, 6) void k_union_cells_pair(
     const float4* __restrict__ pts, Geom g, const int32_t* __restrict__ occ,
     const int32_t* __restrict__ n_occ, const CellRec<2>* __restrict__ crec,
@@ -533,7 +554,7 @@ __global__ __launch_bounds__(kBlock, 6) void k_union_cells_pair(
             if (cb[k] >= 0 && ((wb[k] >> (cb[k] & 31)) & 1u)) {
               const CellRec<2> cr = crec[cb[k]];
               const int r = rep[cb[k]];
-              const uint8_t m = mutual[cb[k]];
+              const uint8_t m = CORE ? (uint8_t)1 : mutual[cb[k]];
               if (r >= 0 && m) {
                 rb[k] = r;
                 cls[k] = classify_cells<2>(A1, rec_boxA<2>(cr), A2, rec_boxB(cr), g);
