@@ -5,66 +5,12 @@
 #include <cstring>
 
 #include "common.h"
+#include "dist.h"
+#include "land.h"
 #include "polar.h"
-
-namespace rpt {
-void release_scratch_current();
-int32_t label_means(const int32_t* labels, const float* x, const float* y, const float* inten,
-                    int64_t n, int64_t n_labels, int64_t* o_count, float* o_x, float* o_y,
-                    float* o_v, hipStream_t st);
-int32_t stdbscan_denoise(const float* x, const float* y, const float* t, int64_t n,
-                         double eps_space, double eps_time, int32_t min_samples,
-                         int32_t min_frames, int32_t* labels, rpt_stdbscan_stats* stats,
-                         hipStream_t st);
-int32_t stdbscan(const float* x, const float* y, const float* z, int64_t stride, const float* t,
-                 int64_t n, double eps_space, double eps_time, int32_t min_samples,
-                 int32_t* labels, rpt_stdbscan_stats* stats, hipStream_t st, int dim);
-int32_t bounds_xy(const float* x, const float* y, int64_t n, float* out4, hipStream_t st);
-int32_t land_grid(const float* x, const float* y, const float* val, int64_t n, const double* xe,
-                  int32_t nxe, const double* ye, int32_t nye, int32_t* cnt, double* tot,
-                  hipStream_t st);
-int32_t land_mask(const int32_t* cnt, const double* tot, int64_t cells, int64_t num_frames,
-                  double pthr, double ithr, uint8_t* land, int64_t* n_land_host,
-                  hipStream_t st);
-int32_t land_filter(const float* x, const float* y, const float* v, const int32_t* g,
-                    const int32_t* pf, int64_t n, const int64_t* frame_off, int32_t n_frames,
-                    const double* xe, int32_t nxe, const double* ye, int32_t nye,
-                    const uint8_t* land, float* xo, float* yo, float* vo, int32_t* go,
-                    int32_t* pfo, int64_t* new_off, int64_t* n_kept_host, hipStream_t st);
-int32_t cluster_summaries(const int32_t* labels, const float* x, const float* y,
-                          const float* inten, const int32_t* pf, int64_t n, int32_t n_frames,
-                          int32_t n_clusters, int32_t* o_frame, int32_t* o_label,
-                          int64_t* o_count, int64_t* o_first, float* o_cx, float* o_cy,
-                          float* o_mi, int64_t* frame_first_noise, int64_t* n_seg_host,
-                          hipStream_t st);
-struct DbscanState;
-DbscanState* dbscan_create();
-void dbscan_destroy(DbscanState* s);
-int32_t dbscan_build(DbscanState* S, const float* x, const float* y, const float* z,
-                     int64_t stride, const float* t, int64_t n, double eps_space,
-                     double eps_time, int32_t ms, hipStream_t st);
-int32_t dbscan_core(DbscanState* S, uint8_t* core_out, hipStream_t st);
-int32_t dbscan_set_core(DbscanState* S, const uint8_t* core_in, hipStream_t st);
-int32_t dbscan_components(DbscanState* S, int32_t* comp_out, hipStream_t st);
-int32_t dbscan_labels_global(DbscanState* S, const int64_t* rep, const int64_t* reps, int64_t nr,
-                             int32_t* labels, hipStream_t st);
-int32_t remap_components(const int32_t* comp, int64_t n, int64_t base, const int64_t* keys,
-                         const int64_t* vals, int64_t nk, int64_t* out, hipStream_t st);
-int32_t select_roots(const int64_t* rep, int64_t base, int64_t lo, int64_t hi, int64_t* out,
-                     int64_t* count_host, hipStream_t st);
-int32_t text_rows_size(int32_t layout, const float* x, const float* y, const float* z,
-                       const void* tail, int64_t n, int64_t* row_offsets, int64_t* total_host,
-                       int64_t* n_bad_host, hipStream_t st);
-int32_t text_rows_write(int32_t layout, const float* x, const float* y, const float* z,
-                        const void* tail, int64_t n, const int64_t* row_offsets, uint8_t* out,
-                        int64_t out_bytes, hipStream_t st);
-int64_t text_tile_bytes();
-int32_t text_rows_index(const uint8_t* text, int64_t nbytes, int64_t n_rows, uint32_t* row_start,
-                        int64_t* lines_found_host, int64_t* n_bad_host, hipStream_t st);
-int32_t text_rows_parse(const uint8_t* text, int64_t nbytes, const uint32_t* row_start,
-                        int64_t n_rows, int32_t n_cols, float* out, int64_t* n_bad_host,
-                        hipStream_t st);
-}  // namespace rpt
+#include "stdbscan.h"
+#include "summaries.h"
+#include "text.h"
 
 struct rpt_dbscan {
   rpt::DbscanState* s;

@@ -51,6 +51,8 @@ class Scratch {
   size_t off_ = 0;
 };
 Scratch& scratch(hipStream_t st);  // for the current device and this stream
+// frees the current device's scratch arenas, zero pools and scan states
+void release_scratch_current();
 
 // ---- pre-zeroed device words ---------------------------------------------------------------
 // Counters a call needs zeroed (atomic cursors, list lengths).  A driver that runs many calls on
@@ -132,7 +134,7 @@ struct Bounds {
 // that produce the ST-DBSCAN bounds of points they write anyway (the shard window).  add() per
 // point (t_prev: the previous point's t in the set's order, has_prev false for the first point),
 // then block_store() by EVERY thread of a block of kBoundsBlock threads: one partial per block,
-// reduced by stdbscan_bounds_final_dev.
+// reduced by stdbscan_bounds_final_dev (stdbscan.h).
 constexpr int kBoundsBlock = 256;
 struct BoundsAcc {
   uint32_t mn[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
@@ -202,8 +204,6 @@ struct BoundsAcc {
     }
   }
 };
-// the partials of nb blocks -> out (one launch, k_bounds_final)
-int32_t stdbscan_bounds_final_dev(const void* part_dev, int nb, void* out_dev, hipStream_t st);
 
 struct PackList {
   const uint32_t* src[kPackMax];

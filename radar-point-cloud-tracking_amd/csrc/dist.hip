@@ -2,6 +2,7 @@
 // component (its min local original index, shifted to the global point numbering) to its
 // global representative, and list the representatives a rank owns.
 #include "common.h"
+#include "dist.h"
 
 namespace rpt {
 namespace {

@@ -15,11 +15,9 @@
 #include <cstring>
 
 #include "common.h"
+#include "land.h"  // bounds_xy
 
 namespace rpt {
-int32_t bounds_xy(const float* x, const float* y, int64_t n, float* out4, hipStream_t st);
-int32_t exclusive_scan_total_i32(const int32_t* in, int32_t* out, int64_t n, hipStream_t stream);
-
 namespace {
 constexpr int kBlock = 256;
 

@@ -22,6 +22,7 @@
 // i < n_rows (row_start: index <= n_rows).
 #include "common.h"
 #include "parse32.h"
+#include "text.h"
 
 namespace rpt {
 namespace {

@@ -31,21 +31,6 @@
 #include "stack_impl.h"
 
 namespace rpt {
-int32_t dbscan_build_given(DbscanState* S, const float* x, const float* y, const float* t,
-                           int64_t n, double eps_space, double eps_time, int32_t ms,
-                           const void* host_bounds, hipStream_t st);
-int32_t dbscan_labels_global_dev(DbscanState* S, const int64_t* rep, const int64_t* reps,
-                                 const int64_t* nr_dev, int32_t* labels, hipStream_t st);
-int32_t dbscan_core_orig(DbscanState* S, uint8_t* out, hipStream_t st);
-int32_t dbscan_components_edges(DbscanState* S, int32_t* comp_out, int64_t lo_end,
-                                int64_t hi_begin, hipStream_t st);
-void dbscan_uf_arrays(const DbscanState* S, const uint8_t** core, const int32_t** parent,
-                      const int32_t** sorig, int64_t* n);
-int32_t dbscan_core_edges(DbscanState* S, int64_t a0, int64_t a1, uint8_t* out_a, int64_t b0,
-                          int64_t b1, uint8_t* out_b, hipStream_t st);
-int32_t dbscan_set_core_edges(DbscanState* S, const uint8_t* in_a, int64_t a1,
-                              const uint8_t* in_b, int64_t b0, hipStream_t st);
-
 namespace {
 
 constexpr int kHaloHdr = 4;                       // int32 header words of a halo buffer

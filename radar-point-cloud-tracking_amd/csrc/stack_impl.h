@@ -11,73 +11,13 @@
 #include <vector>
 
 #include "common.h"
-#include "polar.h"  // K1 and the small kernels beside it
+#include "dist.h"       // the shard merge's device steps
+#include "land.h"       // bounds, K2 / K3
+#include "polar.h"      // K1 and the small kernels beside it
+#include "stdbscan.h"   // K4-K8, fused and phased
+#include "summaries.h"  // K9, radix_bits_for
 
 namespace rpt {
-int32_t bounds_xy(const float* x, const float* y, int64_t n, float* out4, hipStream_t st);
-int32_t land_grid_cells(const float* x, const float* y, const float* val, int64_t n,
-                        const double* xe, int32_t nxe, const double* ye, int32_t nye,
-                        int32_t* cnt, double* tot, int32_t* cell_out, hipStream_t st,
-                        int32_t u8_vals, int64_t* zero_also = nullptr,
-                        uint16_t* cell16_out = nullptr, const uint8_t* val8 = nullptr);
-int32_t land_mask(const int32_t* cnt, const double* tot, int64_t cells, int64_t num_frames,
-                  double pthr, double ithr, uint8_t* land, int64_t* n_land_host,
-                  hipStream_t st);
-int32_t land_mask_dev(const int32_t* cnt, const double* tot, int64_t cells, int64_t num_frames,
-                      double pthr, double ithr, uint8_t* land, int32_t* n_land_dev,
-                      hipStream_t st);
-int32_t land_compact_dev(const float* x, const float* y, const float* v, const int32_t* g,
-                         const int32_t* pf, int64_t n, const int32_t* cell, const uint8_t* land,
-                         int32_t n_frames, float* xo, float* yo, float* vo, int32_t* go,
-                         int32_t* pfo, float* to, int64_t* new_off, Bounds* bounds_out,
-                         hipStream_t st, int64_t t_base = 0,
-                         const int64_t* frame_off = nullptr, const uint16_t* cell16 = nullptr,
-                         const uint8_t* v8 = nullptr, uint8_t* vo8 = nullptr);
-int32_t stdbscan(const float* x, const float* y, const float* z, int64_t stride, const float* t,
-                 int64_t n, double eps_space, double eps_time, int32_t min_samples,
-                 int32_t* labels, rpt_stdbscan_stats* stats, hipStream_t st, int dim);
-int32_t stdbscan_deferred(const float* x, const float* y, const float* z, int64_t stride,
-                          const float* t, int64_t n, double eps_space, double eps_time,
-                          int32_t min_samples, int32_t* labels, rpt_stdbscan_stats* stats,
-                          hipStream_t st, int dim, const int32_t** n_clusters_dev,
-                          void** state, const void* host_bounds);
-size_t stdbscan_bounds_bytes();
-size_t stdbscan_bounds_part_bytes(int64_t n_max);
-int32_t stdbscan_bounds_dev(const float* x, const float* y, const float* t, int64_t n_max,
-                            const int64_t* n_dev, void* out_dev, void* part_dev, hipStream_t st);
-int32_t stdbscan_fill_stats(void* state, int32_t n_clusters, rpt_stdbscan_stats* stats);
-int32_t stdbscan_core_flags(void* state, int64_t n, uint8_t* out, hipStream_t st);
-int32_t cluster_summaries_dev(const int32_t* labels, const float* x, const float* y,
-                              const float* inten, const int32_t* pf, int64_t n, int32_t n_frames,
-                              int bits, int64_t s_hint, int32_t* o_frame, int32_t* o_label,
-                              int64_t* o_count, int64_t* o_first, float* o_cx, float* o_cy,
-                              float* o_mi, int64_t* frame_first_noise,
-                              const int32_t** n_seg_dev, bool force_radix, bool* radix_used,
-                              hipStream_t st, const int64_t* frame_off = nullptr,
-                              const uint8_t* inten8 = nullptr);
-int32_t cluster_summaries(const int32_t* labels, const float* x, const float* y,
-                          const float* inten, const int32_t* pf, int64_t n, int32_t n_frames,
-                          int32_t n_clusters, int32_t* o_frame, int32_t* o_label,
-                          int64_t* o_count, int64_t* o_first, float* o_cx, float* o_cy,
-                          float* o_mi, int64_t* frame_first_noise, int64_t* n_seg_host,
-                          hipStream_t st);
-
-int32_t remap_components(const int32_t* comp, int64_t n, int64_t base, const int64_t* keys,
-                         const int64_t* vals, int64_t nk, int64_t* out, hipStream_t st);
-int32_t select_roots(const int64_t* rep, int64_t base, int64_t lo, int64_t hi, int64_t* out,
-                     int64_t* count_host, hipStream_t st);
-struct DbscanState;
-DbscanState* dbscan_create();
-void dbscan_destroy(DbscanState* s);
-int32_t dbscan_build(DbscanState* S, const float* x, const float* y, const float* z,
-                     int64_t stride, const float* t, int64_t n, double eps_space,
-                     double eps_time, int32_t ms, hipStream_t st);
-int32_t dbscan_core(DbscanState* S, uint8_t* core_out, hipStream_t st);
-int32_t dbscan_set_core(DbscanState* S, const uint8_t* core_in, hipStream_t st);
-int32_t dbscan_components(DbscanState* S, int32_t* comp_out, hipStream_t st);
-int32_t dbscan_labels_global(DbscanState* S, const int64_t* rep, const int64_t* reps, int64_t nr,
-                             int32_t* labels, hipStream_t st);
-
 
 std::vector<double> arange_edges(float lo, float hi, double res);
 
@@ -93,12 +33,6 @@ struct SegPack {
 };
 inline size_t seg_pack_bytes(int64_t sc, int32_t F) {
   return 16 + (size_t)sc * (8 + 8 + 4 + 4 + 4 + 4 + 4) + (size_t)F * 8;
-}
-
-inline int radix_bits_for(int64_t v) {
-  int bits = 1;
-  while ((int64_t(1) << bits) <= v) ++bits;
-  return bits;
 }
 
 template <class T>

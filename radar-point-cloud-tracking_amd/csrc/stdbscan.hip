@@ -45,6 +45,7 @@
 
 #include "common.h"
 #include "dispatch.h"  // with_bool, with_dim
+#include "stdbscan.h"
 
 #pragma clang fp contract(off)
 
@@ -1307,12 +1308,7 @@ int32_t stdbscan_denoise(const float* x, const float* y, const float* t, int64_t
   return S->labels_fifo(labels, stats, st);
 }
 
-// The fused path without its readbacks (the native stack driver): the cluster count stays on the
-// device at *n_clusters_dev (nullptr when the parameters are degenerate: stats is then complete)
-// and stdbscan_fill_stats completes stats after the caller has synchronised the stream.
-// Bounds of the 2-D points [0, *n_dev) (n_dev on the device, <= n_max) into out_dev
-// (stdbscan_bounds_bytes(), device): what stdbscan_deferred's build would compute, for a caller
-// that reads them back together with its own results.
+// ---- the bounds passes and the deferred form (the native stack driver; stdbscan.h)
 size_t stdbscan_bounds_bytes() { return sizeof(Bounds); }
 int32_t stdbscan_bounds_dev(const float* x, const float* y, const float* t, int64_t n_max,
                             const int64_t* n_dev, void* out_dev, void* part_dev,
@@ -1331,8 +1327,6 @@ int32_t stdbscan_bounds_final_dev(const void* part_dev, int nb, void* out_dev, h
   RPT_CHECK_LAUNCH();
   return RPT_OK;
 }
-// the partials of a bounds pass of kBoundsBlock-thread blocks (k_bounds here, k_window in the
-// shard driver) over at most n_max points: one per block of grid_for(n_max, kBoundsBlock, 1024)
 static_assert(kBlock == kBoundsBlock, "k_bounds is launched with kBlock threads per block");
 size_t stdbscan_bounds_part_bytes(int64_t n_max) {
   return sizeof(Bounds) * (size_t)grid_for(std::max<int64_t>(n_max, 1), kBoundsBlock, 1024);
@@ -1365,7 +1359,6 @@ int32_t stdbscan_deferred(const float* x, const float* y, const float* z, int64_
   return s_;
 }
 
-// core flags (original order) of the state's last run: the stack driver's K5 result, for tests
 int32_t stdbscan_core_flags(void* state, int64_t n, uint8_t* out, hipStream_t st) {
   DbscanState* S = static_cast<DbscanState*>(state);
   if (!S || S->degenerate || S->n != n || !S->core || !S->sorig) {
@@ -1436,7 +1429,6 @@ int32_t dbscan_components(DbscanState* S, int32_t* comp_out, hipStream_t st) {
   RPT_CHECK_LAUNCH();
   return RPT_OK;
 }
-// the component ids (as dbscan_components) of the original indices outside [lo_end, hi_begin)
 int32_t dbscan_components_edges(DbscanState* S, int32_t* comp_out, int64_t lo_end,
                                 int64_t hi_begin, hipStream_t st) {
   if (lo_end >= hi_begin) return dbscan_components(S, comp_out, st);
@@ -1454,8 +1446,6 @@ int32_t dbscan_components_edges(DbscanState* S, int32_t* comp_out, int64_t lo_en
   RPT_CHECK_LAUNCH();
   return RPT_OK;
 }
-// the union-find state for the shard driver's per-root passes: a core point s is its
-// component's root iff parent[s] == s (the component's minimum original index is sorig[s])
 void dbscan_uf_arrays(const DbscanState* S, const uint8_t** core, const int32_t** parent,
                       const int32_t** sorig, int64_t* n) {
   *core = S->core;
@@ -1467,8 +1457,7 @@ int32_t dbscan_labels_global(DbscanState* S, const int64_t* rep, const int64_t* 
                              int32_t* labels, hipStream_t st) {
   return S->labels_global(rep, reps, nr, labels, st);
 }
-// the frame-sharded driver's forms: grid bounds read back by the caller with its own results
-// (host_bounds: a Bounds), the representative count on the device
+// ---- the frame-sharded driver's forms (stdbscan.h)
 int32_t dbscan_build_given(DbscanState* S, const float* x, const float* y, const float* t,
                            int64_t n, double eps_space, double eps_time, int32_t ms,
                            const void* host_bounds, hipStream_t st) {
@@ -1487,12 +1476,7 @@ int32_t dbscan_labels_global_dev(DbscanState* S, const int64_t* rep, const int64
                                  const int64_t* nr_dev, int32_t* labels, hipStream_t st) {
   return S->labels_global(rep, reps, 0, labels, st, nr_dev);
 }
-// device u8 core flags in the state's sorted order -> original order (out) without a pass
-// the shard driver's edge forms of dbscan_core / dbscan_set_core: core flags of the original
-// indices [a0, a1) -> out_a and [b0, b1) -> out_b (its own edge frames, for the neighbours), and
-// the halo points' flags from their owners (original indices [0, a1) <- in_a, [b0, n) <- in_b):
-// one coalesced index read per sorted point instead of full-length scattered conversions both
-// ways around the halo update
+// the kernels of dbscan_core_edges / dbscan_set_core_edges: one pass over the sorted points
 __global__ void k_core_to_orig_ranges(const uint8_t* __restrict__ core,
                                       const int32_t* __restrict__ sorig, int64_t n, int64_t a0,
                                       int64_t a1, uint8_t* __restrict__ out_a, int64_t b0,

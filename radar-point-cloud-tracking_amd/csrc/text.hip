@@ -30,6 +30,7 @@
 #include "common.h"
 #include "heat.h"
 #include "repr32.h"
+#include "text.h"
 
 namespace rpt {
 namespace {

@@ -8,7 +8,8 @@ line for line, that is the result.  Otherwise (the functions came out in another
 listings are compared per symbol: a function's text from its ``.type NAME,@function`` to its
 ``.size``, and a kernel's ``.amdhsa_kernel NAME`` ... ``.end_amdhsa_kernel`` resource block.  The
 compiler numbers its local labels (.LBB<f>_<b>, .Lfunc_end<f>) by the function's position, so
-that number is masked.  The lines outside those blocks (data symbols, section directives, the
+that number is masked (and the padding before such a line's comment, which follows the number's
+width: the positions change from one to two digits when a kernel is removed).  The lines outside those blocks (data symbols, section directives, the
 metadata) are compared as a sorted multiset.  The two sets of names must be equal and every
 symbol's text, and the lines outside, equal.  Exit status 0: nothing differs.
 """
@@ -34,7 +35,10 @@ def symbols(lines):
         if f or k:
             name = ("text:" if f else "amdhsa:") + (f or k).group(1)
             out[name] = []
-        out[name or REST].append(LOCAL.sub(r"\1N\2", l))
+        m = LOCAL.sub(r"\1N\2", l)
+        if m != l:  # (a label's comment is padded to a column: the number's width moves it)
+            m = re.sub(r"\s+;", " ;", m)
+        out[name or REST].append(m)
         if s == ".end_amdhsa_kernel" or (name and name.startswith("text:") and
                                          s.startswith(".size")):
             name = None
