@@ -438,7 +438,8 @@ void rpt_stack_destroy(rpt_stack* h);
  * a gate enqueue their K1 (count + write) one at a time, in the order they reach it, each behind
  * the previous one on the device -- the HBM-bound K1 passes of concurrent stacks never coincide
  * and always overlap other stacks' latency-bound stages.  NULL detaches.  The gate must outlive
- * every run of the handles attached to it. */
+ * every run of the handles attached to it.  rpt_k1_gate_create makes the gate's events with it
+ * and returns NULL (rpt_last_error says why) when the device refuses one: no gate then. */
 typedef struct rpt_k1_gate rpt_k1_gate;
 rpt_k1_gate* rpt_k1_gate_create(void);
 void rpt_k1_gate_destroy(rpt_k1_gate* g);

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -129,6 +130,13 @@ struct Bounds {
   int32_t n_finite_t;
   int32_t t_descends;     // some t[i] < t[i-1]: the points are not in time order
 };
+// an ordered-u32 key read back from the device as the float it stands for (host side)
+inline float ord2f(uint32_t u) {
+  const uint32_t v = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+  float f;
+  std::memcpy(&f, &v, 4);
+  return f;
+}
 
 // Device accumulator of a Bounds partial with k_bounds' semantics (stdbscan_grid.inc), for kernels
 // that produce the ST-DBSCAN bounds of points they write anyway (the shard window).  add() per

@@ -60,11 +60,7 @@ int32_t bounds_xy(const float* x, const float* y, int64_t n, float* out4, hipStr
   uint32_t h[4];
   RPT_HIP(hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, st));
   RPT_TRY(wait_stream(st));
-  for (int k = 0; k < 4; ++k) {
-    const uint32_t u = h[k];
-    const uint32_t v = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-    std::memcpy(out4 + k, &v, 4);
-  }
+  for (int k = 0; k < 4; ++k) out4[k] = ord2f(h[k]);
   return RPT_OK;
 }
 

@@ -1,5 +1,5 @@
 // ST-DBSCAN, what more than one stage file or the DbscanState driver reads; no kernel is here.
-// In order: kBlock, the order-preserving float keys (f2ord / ord2f) and the DPP row reductions;
+// In order: kBlock, the order-preserving float key (f2ord) and the DPP row reductions;
 // the grid geometry (FastDiv, Geom, cell_of, slab_of) and the sorted-point layouts (PtRec,
 // Pt<XY>, load_pt, store_pt, slab_time_of); occupied, the launch grids of the persistent kernels
 // (wave_grid, tile_grid), the wave reductions and the cell record (CellRec<D>, rec_boxA /
@@ -19,12 +19,7 @@ __device__ __forceinline__ uint32_t f2ord(float f) {
   uint32_t u = __float_as_uint(f);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
-inline float ord2f(uint32_t u) {  // host side
-  uint32_t v = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-  float f;
-  std::memcpy(&f, &v, 4);
-  return f;
-}
+// (ord2f, the host's way back: common.h)
 
 // ---------------------------------------------------------------- cross-lane reductions by DPP
 // __shfl_xor compiles to a ds_bpermute round trip through LDS, each one waited for; DPP moves

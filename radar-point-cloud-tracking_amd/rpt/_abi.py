@@ -333,3 +333,11 @@ def check(status: int, what: str = "") -> None:
     if status == RPT_ENOMEM:
         raise MemoryError(msg)
     raise RptError(msg)
+
+
+def k1_gate_create():
+    """rpt_k1_gate_create; raises when the library returns NULL (the gate's events failed)."""
+    g = load().rpt_k1_gate_create()
+    if not g:
+        raise RptError(f"rpt_k1_gate_create: {last_error() or 'returned NULL'}")
+    return g

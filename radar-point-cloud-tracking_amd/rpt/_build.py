@@ -57,8 +57,8 @@ def _sources() -> list[Path]:
 
 
 def _headers_mtime() -> float:
-    # (*.inc: kernel sources included by one .hip: the stage files of stdbscan.hip, polar.hip,
-    # summaries.hip and land.hip, the A/B-only stdbscan_ab.inc)
+    # (*.inc: kernel sources included by one unit: the stage files of stdbscan.hip, polar.hip,
+    # summaries.hip, land.hip and shard.cpp, the A/B-only stdbscan_ab.inc)
     hs = list(CSRC.glob("*.h")) + list(CSRC.glob("*.inc")) + list(INCLUDE.glob("*.h"))
     return max((h.stat().st_mtime for h in hs), default=0.0)
 

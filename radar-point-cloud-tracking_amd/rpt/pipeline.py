@@ -110,7 +110,7 @@ class FrameStackPipeline:
             raise ValueError("lanes must be >= 1")
         self._hs = [self.lib.rpt_stack_create() for _ in range(lanes)]
         self._h = self._hs[0]
-        self._gate = self.lib.rpt_k1_gate_create() if lanes > 1 and k1_gate else None
+        self._gate = _abi.k1_gate_create() if lanes > 1 and k1_gate else None
         for h in self._hs if self._gate else []:
             _abi.check(self.lib.rpt_stack_set_k1_gate(h, self._gate), "rpt_stack_set_k1_gate")
         self._streams = [torch.cuda.Stream(self.dev) for _ in range(lanes)] if lanes > 1 else None

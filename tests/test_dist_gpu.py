@@ -46,7 +46,10 @@ def _run(world, frames, impl, lanes, extra, timeout=600, backend="gloo"):
                                                      (3, 6, "native-tinycaps", 1),
                                                      (4, 4, "native-tinycaps", 2),
                                                      (3, 6, "native-hostmerge", 1),
-                                                     (2, 8, "native-hostmerge", 2)])
+                                                     (2, 8, "native-hostmerge", 2),
+                                                     (2, 2, "native-bins512", 1),
+                                                     (2, 6, "native-bins512", 1),
+                                                     (3, 6, "native-emptyrank", 1)])
 def test_sharded_gpu_matches_single_gpu(world, frames, impl, lanes):
     """lanes = 2 / 3: stacks in flight (rpt.dist.ShardLanes: a stream and thread per lane, every
     lane's collectives through the ONE process group in the CommSequencer's software-pipeline
@@ -54,12 +57,23 @@ def test_sharded_gpu_matches_single_gpu(world, frames, impl, lanes):
     the pair and packed-result gathers, so every step is finished again with grown capacities
     (the redo slot).  native-hostmerge: device merge limit 0, so every step's equivalence pairs
     are merged on the host (rpt_merge_equivalences, rpt/dist.py's flag-2 branch of the redo
-    slot: the path a merge of more than 8192 ids takes) and the step finished again with them."""
+    slot: the path a merge of more than 8192 ids takes) and the step finished again with them.
+    native-bins512: 512 x 512 sweeps, K1's generic per-row kernels, whose write leaves no xy
+    bounds, so rpt_shard_polar runs its own bounds pass (k_init_bounds, k_xy_bounds_part); 2 x 2
+    frames with the land filter off (4 built frames: with the dense redo-slot cases and the RCCL
+    world-1 cases below, which also stay at 10 built frames or fewer, what launches k_window),
+    2 x 6 with it on (the bounds are the land grid's edges).  native-emptyrank: the middle rank of 3 x 6 frames has no K1 point while the
+    land filter is on (12 built frames): rpt_shard_halo's empty offsets and k_empty_bounds, and a
+    window of halo points only."""
     extra = []
     if impl == "native-tinycaps":
         impl, extra = "native", ["--tiny-caps"]
     elif impl == "native-hostmerge":
         impl, extra = "native", ["--force-host-merge"]
+    elif impl == "native-bins512":
+        impl, extra = "native", ["--rows", "512", "--bins", "512"]
+    elif impl == "native-emptyrank":
+        impl, extra = "native", ["--rows", "512", "--empty-rank", "1"]
     # rank 0 checks every run against the oracle's run_path over the whole stack as well
     # (labels, per-frame cluster rows in reference order, tracked objects), not only against
     # the single-GPU pipeline

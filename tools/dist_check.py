@@ -33,6 +33,11 @@ def main():
     ap.add_argument("--backend", default="gloo")
     ap.add_argument("--frames", type=int, default=14, help="frames per rank")
     ap.add_argument("--rows", type=int, default=4096)
+    ap.add_argument("--bins", type=int, default=1024,
+                    help="range samples per row; other than 1024: K1's generic per-row kernels, "
+                         "whose write leaves no bounds (the shard driver's own bounds pass)")
+    ap.add_argument("--empty-rank", type=int, default=-1,
+                    help="that rank's sweeps hold no sample: a rank without a K1 point")
     ap.add_argument("--lanes", type=int, default=1,
                     help="native: stacks in flight (rpt.dist.ShardLanes); every lane's result "
                          "is checked")
@@ -90,6 +95,8 @@ def main():
     cfg = _config(args, F, rank * F)
     ds = DeviceSynth(cfg, dev)
     echo = ds.echo()
+    if rank == args.empty_rank:
+        echo.zero_()
     runs = []  # (result, this rank's labels) per checked run
     if args.impl == "native" and args.lanes > 1:
         from rpt.dist import ShardLanes
@@ -350,8 +357,16 @@ def _config(args, n_frames, frame0=0):
     from rpt.synth import SynthConfig, dense_config
 
     if args.dense:
-        return dense_config(n_frames=n_frames, rows=args.rows, frame0=frame0)
-    return SynthConfig(n_frames=n_frames, rows=args.rows, frame0=frame0)
+        return dense_config(n_frames=n_frames, rows=args.rows, bins=args.bins, frame0=frame0)
+    return SynthConfig(n_frames=n_frames, rows=args.rows, bins=args.bins, frame0=frame0)
+
+
+def _whole_echo(dsf, args):
+    """The whole stack's echo as the ranks saw it (--empty-rank: that rank's frames blank)."""
+    echo = dsf.echo()
+    if args.empty_rank >= 0:
+        echo[args.empty_rank * args.frames:(args.empty_rank + 1) * args.frames].zero_()
+    return echo
 
 
 _ORACLE = {}
@@ -372,7 +387,7 @@ def check_oracle(res, labels, world, args, dev):
     if key not in _ORACLE:   # once per stack (every lane's last run is checked)
         full = _config(args, args.frames * world)
         dsf = DeviceSynth(full, dev)
-        frames = oracle_stack(dsf.echo().cpu().numpy(), full, dsf.geo)
+        frames = oracle_stack(_whole_echo(dsf, args).cpu().numpy(), full, dsf.geo)
         _ORACLE[key] = op.run_path(frames, dbscan=oracle.stdbscan_uf)
     o_frames, o_labels, o_clusters, o_trk = _ORACLE[key]
     got = torch.cat([l.cpu() for l in labels]).numpy()
@@ -412,7 +427,7 @@ def check(res, labels, rank, world, args, dev):
         single = FrameStackPipeline(full.gains, full.rows, full.bins, PathParams(), dev)
         single.set_geometry(np.full(full.rows, full.scale, np.float32), dsf.geo.cos_t,
                             dsf.geo.sin_t, full.n_frames * 3)
-        ref = single.run(dsf.echo(), keep_points=True)
+        ref = single.run(_whole_echo(dsf, args), keep_points=True)
         got = torch.cat([l.cpu() for l in labels]).numpy()
         exp = ref.labels.cpu().numpy().astype(np.int64)
         ok &= bool(np.array_equal(got, exp))
