@@ -17,6 +17,8 @@
  *   rpt_stdbscan                     st_dbscan  PointCloudWork/3_stdbscan_point_clouds.py:101-136,
  *                                     radar_pipeline/processors/clustering.py:49-115,
  *                                     the labelling half of 4_temporal_object_tracker.py:443-506
+ *   rpt_stdbscan_f64                 the same st_dbscan on float64 coordinates / float64 times
+ *   rpt_grid64_plan / _index         its grid rule on the host (no GPU)
  *   rpt_infer_time_from_colors       radar_pipeline/processors/clustering.py:17-46, 3_stdbscan...py:91-98
  *   rpt_cluster_summaries            per-frame Cluster extraction 4_temporal_object_tracker.py:508-536
  *   rpt_set_order                    CPython set(frame_labels) iteration order :519
@@ -191,6 +193,35 @@ int32_t rpt_stdbscan(const float* x, const float* y, const float* z, int64_t str
                      const float* times, int64_t n, double eps_space, double eps_time,
                      int32_t min_samples, int32_t* labels, rpt_stdbscan_stats* stats,
                      void* stream);
+/* The same contract on float64 coordinates (x, y, z: device doubles sharing `stride`; z NULL:
+ * 2-D), for inputs that float32 cannot hold: decimal columns, projected coordinates with large
+ * offsets, epoch times.  d2 as above on the doubles themselves.  times: n contiguous device
+ * values of time_dtype; RPT_TIME_F32: |f32(t_j - t_i)| <= f32(eps_time) as rpt_stdbscan,
+ * RPT_TIME_F64: float64 |t_j - t_i| <= eps_time.  A point with a NaN or infinite time is
+ * nobody's neighbour, not even its own.  Numbering, errors, degenerate parameters (eps_time
+ * tested in double for RPT_TIME_F64) and stats as rpt_stdbscan; an unknown time_dtype is
+ * RPT_EINVAL.  Synchronises for the grid bounds, and for the cluster count when stats is given.
+ * No per-cell screens: every pair of a point's 3^dim x 3 cell window is tested exactly. */
+enum { RPT_TIME_F32 = 0, RPT_TIME_F64 = 1 };
+int32_t rpt_stdbscan_f64(const double* x, const double* y, const double* z /*NULL: 2-D*/,
+                         int64_t stride, const void* times, int32_t time_dtype, int64_t n,
+                         double eps_space, double eps_time, int32_t min_samples,
+                         int32_t* labels, rpt_stdbscan_stats* stats, void* stream);
+/* The grid rule of rpt_stdbscan_f64 on the host (no GPU; csrc/grid64.h): the grid of a point
+ * set with the given minima / maxima (lo4 / hi4: x, y, z, t over the finite values; index 2
+ * ignored for dim 2), n_finite_t finite times and n points, for eps_space >= 0 and
+ * eps_time >= 0 (else RPT_EINVAL); and the cell of a value along an axis of n cells. */
+typedef struct rpt_grid64 {
+  double lo[4];
+  double cs, ct;        /* cell side, slab width                                  */
+  int32_t dims[4];      /* nx, ny, nz, nt                                         */
+  int64_t cells;
+  int32_t doublings;    /* side doublings under the cell cap                      */
+  int32_t collapsed;    /* bit 0: space is one cell, bit 1: time too              */
+} rpt_grid64;
+int32_t rpt_grid64_plan(const double* lo4, const double* hi4, int64_t n_finite_t, int32_t dim,
+                        double eps_space, double eps_time, int64_t n, rpt_grid64* out);
+int32_t rpt_grid64_index(double v, double lo, double side, int32_t n);
 /* Denoise variant (replaces st_dbscan of PointCloudWorkF/stdbscan_denoising_pipeline.py:264-369;
  * 2-D, x / y / times dev float32 [n]): core = >= min_samples neighbours (itself included, same
  * test as rpt_stdbscan) spanning >= min_frames distinct int32(times) frames; clusters numbered by

@@ -9,6 +9,7 @@
 #include "land.h"
 #include "polar.h"
 #include "stdbscan.h"
+#include "stdbscan64.h"
 #include "summaries.h"
 #include "text.h"
 
@@ -119,6 +120,15 @@ int32_t rpt_stdbscan(const float* x, const float* y, const float* z, int64_t str
   const int dim = z ? 3 : 2;
   return rpt::stdbscan(x, y, z, stride, times, n, eps_space, eps_time, min_samples, labels,
                        stats, rpt::as_stream(stream), dim);
+}
+
+int32_t rpt_stdbscan_f64(const double* x, const double* y, const double* z, int64_t stride,
+                         const void* times, int32_t time_dtype, int64_t n, double eps_space,
+                         double eps_time, int32_t min_samples, int32_t* labels,
+                         rpt_stdbscan_stats* stats, void* stream) {
+  rpt::clear_error();
+  return rpt::stdbscan_f64(x, y, z, stride, times, time_dtype, n, eps_space, eps_time,
+                           min_samples, labels, stats, rpt::as_stream(stream));
 }
 
 int32_t rpt_label_means(const int32_t* labels, const float* x, const float* y,

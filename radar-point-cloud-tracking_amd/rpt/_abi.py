@@ -19,6 +19,9 @@ RPT_EEMPTY = 4
 RPT_ENOTSUP = 5
 RPT_ENONFINITE = 6
 
+TIME_F32 = 0
+TIME_F64 = 1
+
 ECHO_F32 = 0
 ECHO_U8 = 1
 
@@ -51,6 +54,18 @@ class StdbscanStats(C.Structure):
         ("ms_union", C.c_double),
         ("ms_label", C.c_double),
         ("timing", C.c_int32),
+    ]
+
+
+class Grid64(C.Structure):
+    _fields_ = [
+        ("lo", C.c_double * 4),
+        ("cs", C.c_double),
+        ("ct", C.c_double),
+        ("dims", C.c_int32 * 4),
+        ("cells", C.c_int64),
+        ("doublings", C.c_int32),
+        ("collapsed", C.c_int32),
     ]
 
 
@@ -181,6 +196,13 @@ _SIGS = [
     ("rpt_stdbscan", C.c_int32,
      [vp, vp, vp, C.c_int64, vp, C.c_int64, C.c_double, C.c_double, C.c_int32, vp,
       C.POINTER(StdbscanStats), vp]),
+    ("rpt_stdbscan_f64", C.c_int32,
+     [vp, vp, vp, C.c_int64, vp, C.c_int32, C.c_int64, C.c_double, C.c_double, C.c_int32, vp,
+      C.POINTER(StdbscanStats), vp]),
+    ("rpt_grid64_plan", C.c_int32,
+     [c_f64p, c_f64p, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_int64,
+      C.POINTER(Grid64)]),
+    ("rpt_grid64_index", C.c_int32, [C.c_double, C.c_double, C.c_double, C.c_int32]),
     ("rpt_label_means", C.c_int32,
      [vp, vp, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp]),
     ("rpt_stdbscan_denoise", C.c_int32,

@@ -8,7 +8,7 @@ stay on their device and a torch int32 tensor comes back.
 from __future__ import annotations
 
 from pathlib import Path
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -24,6 +24,7 @@ def _times_to_f32(times, eps_time: float):
     float32 times: exact (NEP 50 makes the reference compare in float32).  Integer times, or
     float64 times that are all integers below 2^24: |dt| is an exact integer in every precision,
     so ``|dt| <= eps`` equals ``|dt| <= floor(eps)``, which float32 represents exactly.
+    Returns None where the times have no such form (TypeError for a dtype that is no number).
     """
     if is_torch(times):
         dt = times.dtype
@@ -33,8 +34,7 @@ def _times_to_f32(times, eps_time: float):
         fin = torch.isfinite(tt)
         integral = bool(torch.all(~fin | ((tt == torch.floor(tt)) & (tt.abs() < 2**24))))
         if not integral:
-            raise NotImplementedError(
-                f"rpt st_dbscan: non-float32 times ({dt}) must be integral below 2^24")
+            return None
         return tt.to(torch.float32), float(np.floor(eps_time)) if np.isfinite(eps_time) else eps_time
     a = np.asarray(times)
     if a.dtype == np.float32:
@@ -43,42 +43,117 @@ def _times_to_f32(times, eps_time: float):
         af = a.astype(np.float64)
         fin = np.isfinite(af)
         if not np.all(~fin | ((af == np.floor(af)) & (np.abs(af) < 2**24))):
-            raise NotImplementedError(
-                f"rpt st_dbscan: non-float32 times ({a.dtype}) must be integral below 2^24")
+            return None
         e = float(np.floor(eps_time)) if np.isfinite(eps_time) else eps_time
         return af.astype(np.float32), e
     raise TypeError(f"unsupported times dtype {a.dtype}")
 
 
 def _coords_to_f32(coords):
+    """The coordinates as float32 where every value round-trips through float32, else None."""
     if is_torch(coords):
         if coords.dtype == torch.float32:
             return coords
         c32 = coords.to(torch.float32)
         if not torch.equal(c32.to(coords.dtype), coords):
-            raise NotImplementedError("rpt st_dbscan: coordinates must be float32-representable")
+            return None
         return c32
     a = np.asarray(coords)
     if a.dtype == np.float32:
         return a
-    a32 = a.astype(np.float32)
-    with np.errstate(invalid="ignore"):
-        same = np.array_equal(a32.astype(a.dtype), a, equal_nan=True)
+    with np.errstate(invalid="ignore", over="ignore"):  # (beyond float32's range: inf, not equal)
+        a32 = a.astype(np.float32)
+        same =np.array_equal(a32.astype(a.dtype), a, equal_nan=True)
     if not same:
-        raise NotImplementedError("rpt st_dbscan: coordinates must be float32-representable")
+        return None
     return a32
+
+
+_TORCH_INT = (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8, torch.bool)
+
+
+def _times_to_f64(times):
+    """The float64 kernel's times: (values, time dtype), or NotImplementedError.
+
+    float32 stays float32 (the reference compares in float32 under NEP 50) and float64 stays
+    float64.  Integers within +-2^53 become doubles: their differences are exact there, and numpy
+    compares an integer difference with a Python float in float64.  Unsigned times stay exact
+    integers (the reference's wrap-around is not reproduced).  float16, longdouble and integers
+    beyond 2^53 are refused.
+    """
+    if is_torch(times):
+        dt = times.dtype
+        if dt == torch.float32:
+            return times, "float32"
+        if dt == torch.float64:
+            return times, "float64"
+        if dt in _TORCH_INT:
+            lim = 2**53
+            if dt == torch.int64 and bool(torch.any((times < -lim) | (times > lim))):
+                raise NotImplementedError("rpt st_dbscan: integer times beyond 2^53")
+            return times.to(torch.float64), "float64"
+        raise NotImplementedError(f"rpt st_dbscan: times of dtype {dt} are not supported")
+    a = np.asarray(times)
+    if a.dtype == np.float32:
+        return a, "float32"
+    if a.dtype == np.float64:
+        return a, "float64"
+    if a.dtype.kind in "iub":
+        lim = 2**53
+        if a.dtype.kind == "i" and a.dtype.itemsize == 8 and np.any((a < -lim) | (a > lim)):
+            raise NotImplementedError("rpt st_dbscan: integer times beyond 2^53")
+        if a.dtype.kind == "u" and a.dtype.itemsize == 8 and np.any(a > np.uint64(lim)):
+            raise NotImplementedError("rpt st_dbscan: integer times beyond 2^53")
+        return a.astype(np.float64), "float64"
+    if a.dtype.kind == "f":
+        raise NotImplementedError(
+            f"rpt st_dbscan: non-float32 times ({a.dtype}) must be float64, or integral below 2^24 "
+            "with float32-representable coordinates")
+    raise TypeError(f"unsupported times dtype {a.dtype}")
+
+
+class _Plan(NamedTuple):
+    precision: str    # "float32": rpt_stdbscan, "float64": rpt_stdbscan_f64
+    coords: object    # array / tensor of that precision
+    times: object     # float32, or float64 where time_dtype says so
+    time_dtype: str   # "float32" | "float64": the dtype the time test runs in
+    eps_time: float
+
+
+def _plan_inputs(coords, times, eps_time: float) -> _Plan:
+    """Which kernel an input takes, and in which form (host logic only: no kernel is called).
+
+    The float32 route is unchanged: coordinates whose values all round-trip through float32, with
+    float32 times or integral times below 2^24.  Everything else the reference computes goes to
+    the float64 kernel: the coordinates as ``astype(float64)`` (sklearn's check_array makes the
+    same cast; widening float32 is exact) and the times by ``_times_to_f64``.
+    """
+    c32 = _coords_to_f32(coords)
+    if c32 is not None:
+        t32 = _times_to_f32(times, eps_time)
+        if t32 is not None:
+            return _Plan("float32", c32, t32[0], "float32", t32[1])
+    t, time_dtype = _times_to_f64(times)
+    c = coords.to(torch.float64) if is_torch(coords) else np.asarray(coords).astype(np.float64)
+    return _Plan("float64", c, t, time_dtype, eps_time)
 
 
 def st_dbscan(coords, times, eps_space: float, eps_time: float, min_samples: int,
               stats: Optional[dict] = None):
     """Spatio-temporal DBSCAN (clustering.py:49-115; 3_stdbscan_point_clouds.py:101-136).
 
-    coords: (N, 2|3) float32 array/tensor; times: (N,) float32 (integral int/f64 accepted).
+    coords: (N, 2|3) array/tensor; times: (N,).  float32-representable coordinates with float32
+    or small integral times run in the float32 kernels (rpt_stdbscan); other real inputs --
+    float64 decimals, large offsets, integer coordinates above 2^24, float64 or epoch times -- in
+    the float64 kernel (rpt_stdbscan_f64), see ``_plan_inputs``.  ``stats`` reports which as
+    ``precision`` and ``time_dtype``.
     Returns int32 labels, -1 for noise, ids ascending with each cluster's first core point —
     bit-identical to the reference BFS.  Empty input raises ValueError like sklearn's BallTree.
     """
     want_torch = is_torch(coords)
-    c = _coords_to_f32(coords)
+    plan = _plan_inputs(coords, times, float(eps_time))
+    c = plan.coords
+    f64 = plan.precision == "float64"
     shape = tuple(c.shape)
     if len(shape) != 2:
         raise ValueError(f"Expected 2D array, got {len(shape)}D array instead")
@@ -88,27 +163,35 @@ def st_dbscan(coords, times, eps_space: float, eps_time: float, min_samples: int
             f"Found array with 0 sample(s) (shape=(0, {dim})) while a minimum of 1 is required.")
     if dim not in (2, 3):
         raise NotImplementedError(f"rpt st_dbscan supports 2 or 3 coordinates, got {dim}")
-    t, eps_t = _times_to_f32(times, float(eps_time))
+    t, eps_t = plan.times, plan.eps_time
     if (t.shape[0] if is_torch(t) else len(t)) != n:
         raise ValueError("coords and times must have the same length")
     dev = require_gpu(c.device if is_torch(c) else None)
-    cd = to_device(c, torch.float32, dev)
-    td = to_device(t, torch.float32, dev)
+    cd = to_device(c, torch.float64 if f64 else torch.float32, dev)
+    td = to_device(t, torch.float64 if plan.time_dtype == "float64" else torch.float32, dev)
     labels = torch.empty(n, dtype=torch.int32, device=dev)
     lib = _abi.load()
     st = _abi.StdbscanStats()
     st.timing = 1 if stats is not None else 0
     base = cd.data_ptr()
     with torch.cuda.device(dev):
-        status = lib.rpt_stdbscan(base, base + 4, (base + 8) if dim == 3 else None, dim,
-                                  td.data_ptr(), n, float(eps_space), float(eps_t),
-                                  int(min_samples), labels.data_ptr(), st,
-                                  stream_handle(dev))
-    _abi.check(status, "rpt_stdbscan")
+        if f64:
+            status = lib.rpt_stdbscan_f64(
+                base, base + 8, (base + 16) if dim == 3 else None, dim, td.data_ptr(),
+                _abi.TIME_F64 if plan.time_dtype == "float64" else _abi.TIME_F32, n,
+                float(eps_space), float(eps_t), int(min_samples), labels.data_ptr(), st,
+                stream_handle(dev))
+        else:
+            status = lib.rpt_stdbscan(base, base + 4, (base + 8) if dim == 3 else None, dim,
+                                      td.data_ptr(), n, float(eps_space), float(eps_t),
+                                      int(min_samples), labels.data_ptr(), st,
+                                      stream_handle(dev))
+    _abi.check(status, "rpt_stdbscan_f64" if f64 else "rpt_stdbscan")
     if stats is not None:
         stats.update(n_clusters=st.n_clusters, grid_dims=tuple(st.grid_dims),
                      grid_cells=st.grid_cells, ms_bounds=st.ms_bounds, ms_grid=st.ms_grid,
-                     ms_core=st.ms_core, ms_union=st.ms_union, ms_label=st.ms_label)
+                     ms_core=st.ms_core, ms_union=st.ms_union, ms_label=st.ms_label,
+                     precision=plan.precision, time_dtype=plan.time_dtype)
     if want_torch:
         return labels
     return labels.cpu().numpy()
