@@ -39,6 +39,9 @@
  *   rpt_heat_colors                  and intensity_to_rgb :292-327, per segment (frame) of one array;
  *   (RPT_TEXT_PLY4)                  the np.savetxt rows of write_ply_fast :370-403
  *   rpt_heat_host / rpt_fixed4_repr  the per-value code of those three on the host (no GPU)
+ *   rpt_ply_records_size / _write /  write_ply PointCloudWorkF/stdbscan_denoising_pipeline.py:767-855 with
+ *   rpt_ply_colors                   the [signal_mask] indexing of run_pipeline :1000-1003 inside it
+ *   rpt_ply_records_host             the per-value code of those on the host (no GPU)
  *   rpt_synth_echo                   (bench/test input generator; no reference counterpart)
  */
 #ifndef RPT_H
@@ -407,6 +410,56 @@ int32_t rpt_heat_host(const float* v, int64_t n, const int64_t* seg_off, int64_t
                       int32_t colors_only, float* seg_min, float* seg_p99, float* z, uint8_t* rgb);
 #define RPT_FIXED4_SLOT 20
 int32_t rpt_fixed4_repr(const float* v, int64_t n, char* out /*[n][20]*/, int32_t* len /*[n]*/);
+
+/* ---- binary PLY records of the denoise pipeline (stdbscan_denoising_pipeline.py write_ply
+ * :767-855) ---------------------------------------------------------------------------------
+ * Point i of x, y, z (dev, float32 [n]) with an optional label (dev, int32 [n]) becomes one
+ * 15-byte record: the three float32 bit patterns little-endian, unchanged (NaN payloads kept),
+ * then r, g, b.  A point is KEPT when labels == NULL, or signal_only == 0, or labels[i] >= 0
+ * (signal_only != 0 is the caller's [labels >= 0] indexing done here); kept points keep their
+ * input order.  Colours, from a LUT the caller takes from its colour maps (dev, uint8):
+ *   with labels     lut [20][3]:  lut[labels[i] % 20] for labels[i] >= 0, (128, 128, 128) for
+ *                   any negative label
+ *   without labels  lut [257][3]: row idx of z[i], as matplotlib evaluates
+ *                   viridis(np.clip(z / 255.0, 0, 1)) on a float32 array:
+ *                     zn = clip(z / 255.0f, 0, 1)   (IEEE float32 division)
+ *                     f = zn * 256.0f;  idx = f == 256.0f ? 255 : (int)f
+ *                   a NaN takes row 256 (the map's "bad" colour), -inf row 0, +inf row 255.
+ * n < 2^31, else RPT_ENOTSUP; n == 0 is legal; signal_only != 0 with labels == NULL is RPT_EINVAL.
+ *
+ * rpt_ply_record_tiles (host only): the passes work on tiles of 1024 points; the tile count of n.
+ * rpt_ply_records_size: tile_offsets (dev int64 [tiles + 1]) = exclusive scan of the kept points
+ * per tile with the total at [tiles]; *n_kept_host = that total and *max_label_host (may be NULL)
+ * = the largest label of all n points, -1 when there is none >= 0 (or no labels) are read back
+ * (synchronises once).
+ * rpt_ply_records_write: the kept points' records at out + 15 * rank (out dev u8 [out_bytes],
+ * out_bytes >= 15 * kept).  The inputs must be those given to rpt_ply_records_size; a tile whose
+ * byte range, as its offsets give it, does not lie inside [0, out_bytes) or does not match the
+ * tile's own kept count is skipped -- nothing is written outside out whatever the inputs hold.
+ * No sync.
+ * rpt_ply_colors: the colours alone, of every point (rgb dev u8 [n][3]); z is not read with
+ * labels (may be NULL), labels NULL selects the intensity map.  No sync.
+ * rpt_ply_records_host (host only, no GPU): keep rule, colours and records over host arrays by
+ * the same per-value code (csrc/plyrec.h).  Returns the kept count, or -RPT_E* (negative) for
+ * bad arguments; out == NULL counts only, else kept * 15 <= out_bytes is required before a byte
+ * is written; *max_label (may be NULL) as above. */
+int64_t rpt_ply_record_tiles(int64_t n);
+int32_t rpt_ply_records_size(const int32_t* labels /*dev [n] or NULL*/, int64_t n,
+                             int32_t signal_only, int64_t* tile_offsets /*dev [tiles + 1]*/,
+                             int64_t* n_kept_host, int32_t* max_label_host /*nullable*/,
+                             void* stream);
+int32_t rpt_ply_records_write(const float* x, const float* y, const float* z,
+                              const int32_t* labels /*nullable*/, int32_t signal_only,
+                              const uint8_t* lut /*dev*/, int64_t n,
+                              const int64_t* tile_offsets /*dev*/, uint8_t* out /*dev [out_bytes]*/,
+                              int64_t out_bytes, void* stream);
+int32_t rpt_ply_colors(const float* z /*nullable*/, const int32_t* labels /*nullable*/,
+                       const uint8_t* lut /*dev*/, int64_t n, uint8_t* rgb /*dev [n][3]*/,
+                       void* stream);
+int64_t rpt_ply_records_host(const float* x, const float* y, const float* z,
+                             const int32_t* labels /*nullable*/, int32_t signal_only,
+                             const uint8_t* lut, int64_t n, uint8_t* out /*[out_bytes] or NULL*/,
+                             int64_t out_bytes, int32_t* max_label /*nullable*/);
 
 /* ---- K9: per-(frame, label) cluster summaries ---------------------------------------
  * point_frame[n] (dev, i32, non-decreasing frame slot per point), labels[n] from

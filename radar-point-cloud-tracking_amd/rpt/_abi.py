@@ -31,6 +31,7 @@ TEXT_XYZ_REPR = 2
 TEXT_PLY4 = 3
 FLOAT32_REPR_SLOT = 20
 FIXED4_SLOT = 20
+PLY_RECORD = 15        # bytes of one binary PLY record (csrc/plyrec.h)
 
 c_f32p = C.POINTER(C.c_float)
 c_f64p = C.POINTER(C.c_double)
@@ -291,6 +292,13 @@ _SIGS = [
      [vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int32, vp, vp, vp]),
     ("rpt_heat_host", C.c_int32, [vp, C.c_int64, vp, C.c_int64, C.c_int32, vp, vp, vp, vp]),
     ("rpt_fixed4_repr", C.c_int32, [vp, C.c_int64, vp, vp]),
+    ("rpt_ply_record_tiles", C.c_int64, [C.c_int64]),
+    ("rpt_ply_records_size", C.c_int32, [vp, C.c_int64, C.c_int32, vp, c_i64p, c_i32p, vp]),
+    ("rpt_ply_records_write", C.c_int32,
+     [vp, vp, vp, vp, C.c_int32, vp, C.c_int64, vp, vp, C.c_int64, vp]),
+    ("rpt_ply_colors", C.c_int32, [vp, vp, vp, C.c_int64, vp, vp]),
+    ("rpt_ply_records_host", C.c_int64,
+     [vp, vp, vp, vp, C.c_int32, vp, C.c_int64, vp, C.c_int64, c_i32p]),
     ("rpt_csv_count_rows", C.c_int32, [C.POINTER(C.c_char_p), C.c_int32, c_i64p, C.c_int32]),
     ("rpt_csv_parse_sweeps", C.c_int32,
      [C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, c_f32p, c_f32p,

@@ -13,7 +13,9 @@ The pipeline around it (run_pipeline :862-1046) keeps the reference's file disco
 2-second frame grouping (:155-216), loads every sweep through the native CSV parser and the K1
 kernels (threshold 10, stride 4, gains concatenated in the frame's time order, :97-152 /
 :219-231), stamps each point with its frame index (empty frames keep their index, :933-940), and
-writes the same outputs: the binary PLYs (:767-855), denoising_stats.csv and clusters.csv (the
+writes the same outputs: the binary PLYs (:767-855; the ``labels >= 0`` indexing, the tab20 /
+viridis colours and the 15-byte records formed on the device by csrc/plyrec.hip, so that only the
+file bodies cross to the host), denoising_stats.csv and clusters.csv (the
 pandas group means of :997-1012, computed by ``rpt_label_means``).  The PNG / GIF visualisations
 (:1015-1041) are not built: matplotlib rendering is outside this engine's scope.
 """
@@ -321,10 +323,120 @@ def cluster_table(labels: torch.Tensor, x: torch.Tensor, y: torch.Tensor, z: tor
                          "mean_intensity": mz.cpu().numpy()[:n_clusters][keep]})
 
 
-def write_ply(path: Path, x: np.ndarray, y: np.ndarray, z: np.ndarray,
-              labels: Optional[np.ndarray] = None, use_binary: bool = True) -> None:
-    """:767-855 -- file formatting on the host: tab20 colours by label % 20 (noise grey 128),
-    or viridis of intensity / 255 without labels, exactly as the reference evaluates them."""
+_PLY_HEADER = ("ply\nformat {fmt} 1.0\nelement vertex {n}\n"
+               "property float x\nproperty float y\nproperty float z\n"
+               "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
+_REC = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("r", "u1"), ("g", "u1"), ("b", "u1")])
+
+_luts: dict = {}
+
+
+def ply_luts() -> Tuple[np.ndarray, np.ndarray]:
+    """The colour tables of write_ply (:786-795) from the installed matplotlib, once per process:
+    tab20 as uint8 [20][3] and viridis as uint8 [257][3], row 256 the colour of a NaN."""
+    if "host" not in _luts:
+        import matplotlib
+
+        cmap = matplotlib.colormaps["tab20"]
+        viridis = matplotlib.colormaps["viridis"]
+        lut20 = (np.array([cmap(i)[:3] for i in range(20)]) * 255).astype(np.uint8)
+        lutv = (viridis(np.arange(256))[:, :3] * 255).astype(np.uint8)
+        bad = (viridis(np.array([np.nan], np.float32))[:, :3] * 255).astype(np.uint8)
+        _luts["host"] = (np.ascontiguousarray(lut20),
+                         np.ascontiguousarray(np.concatenate([lutv, bad])))
+    return _luts["host"]
+
+
+def _lut_device(with_labels: bool, dev: torch.device) -> torch.Tensor:
+    key = (with_labels, dev)
+    if key not in _luts:
+        _luts[key] = torch.from_numpy(ply_luts()[0 if with_labels else 1]).to(dev)
+    return _luts[key]
+
+
+def ply_records_host(x, y, z, labels=None, signal_only: bool = False, lut=None):
+    """The binary records of write_ply over host arrays by librpt's host twin of the kernels
+    (rpt_ply_records_host, no GPU): (bytes of the kept points' records, kept count, largest
+    label or -1).  lut: the colour table of the mode ([20][3] with labels, [257][3] without);
+    None takes ply_luts()'s."""
+    lib = _abi.load()
+    x, y, z = (np.ascontiguousarray(a, np.float32) for a in (x, y, z))
+    n = len(x)
+    lab = None if labels is None else np.ascontiguousarray(labels, np.int32)
+    if lut is None:
+        lut = ply_luts()[0 if lab is not None else 1]
+    lut = np.ascontiguousarray(lut, np.uint8)
+    out = np.empty(_abi.PLY_RECORD * n, np.uint8)
+    mx = _abi.C.c_int32(-1)
+    kept = lib.rpt_ply_records_host(x.ctypes.data, y.ctypes.data, z.ctypes.data,
+                                    None if lab is None else lab.ctypes.data, int(signal_only),
+                                    lut.ctypes.data, n, out.ctypes.data, out.size,
+                                    _abi.C.byref(mx))
+    if kept < 0:
+        _abi.check(int(-kept), "rpt_ply_records_host")
+    return out[:_abi.PLY_RECORD * kept].tobytes(), int(kept), int(mx.value)
+
+
+def ply_records_size(labels: Optional[torch.Tensor], n: int, signal_only: bool, dev):
+    """rpt_ply_records_size: (tile offsets on the device, kept count, largest label or -1) of n
+    points with device int32 labels (None: every point kept).  Synchronises once."""
+    lib = _abi.load()
+    tiles = int(lib.rpt_ply_record_tiles(n))
+    offsets = torch.empty(tiles + 1, dtype=torch.int64, device=dev)
+    kept = _abi.C.c_int64(0)
+    mx = _abi.C.c_int32(-1)
+    with torch.cuda.device(dev):
+        _abi.check(lib.rpt_ply_records_size(None if labels is None else labels.data_ptr(), n,
+                                            int(signal_only), offsets.data_ptr(),
+                                            _abi.C.byref(kept), _abi.C.byref(mx),
+                                            stream_handle(dev)), "rpt_ply_records_size")
+    return offsets, int(kept.value), int(mx.value)
+
+
+def ply_records_device(x, y, z, labels=None, signal_only: bool = False, lut=None, size=None):
+    """The kept points' records of contiguous device tensors (x, y, z float32 [n], labels int32
+    [n] or None) as a device uint8 tensor [15 * kept] (rpt_ply_records_size / _write).  size:
+    what ply_records_size returned for these labels and signal_only (None: it is called here)."""
+    dev = x.device
+    n = int(x.numel())
+    if lut is None:
+        lut = _lut_device(labels is not None, dev)
+    offsets, kept, _ = size or ply_records_size(labels, n, signal_only, dev)
+    out = torch.empty(_abi.PLY_RECORD * kept, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _abi.check(_abi.load().rpt_ply_records_write(
+            x.data_ptr(), y.data_ptr(), z.data_ptr(),
+            None if labels is None else labels.data_ptr(), int(signal_only), lut.data_ptr(), n,
+            offsets.data_ptr(), out.data_ptr(), out.numel(), stream_handle(dev)),
+            "rpt_ply_records_write")
+    return out
+
+
+def ply_colors_device(z, labels=None, lut=None) -> torch.Tensor:
+    """The colours of write_ply alone, uint8 [n][3] on the device (rpt_ply_colors): tab20 by
+    label with device int32 labels, else viridis by the device float32 intensities z."""
+    src = labels if labels is not None else z
+    dev = src.device
+    n = int(src.numel())
+    if lut is None:
+        lut = _lut_device(labels is not None, dev)
+    rgb = torch.empty((n, 3), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _abi.check(_abi.load().rpt_ply_colors(
+            None if labels is not None else z.data_ptr(),
+            None if labels is None else labels.data_ptr(), lut.data_ptr(), n, rgb.data_ptr(),
+            stream_handle(dev)), "rpt_ply_colors")
+    return rgb
+
+
+def _as_host(a) -> np.ndarray:
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
+
+
+def write_ply_host(path: Path, x: np.ndarray, y: np.ndarray, z: np.ndarray,
+                   labels: Optional[np.ndarray] = None, use_binary: bool = True) -> None:
+    """:767-855 on the host, the reference's expressions themselves: tab20 colours by label % 20
+    (noise grey 128), or viridis of intensity / 255 without labels."""
     import matplotlib
 
     num_points = len(x)
@@ -342,22 +454,15 @@ def write_ply(path: Path, x: np.ndarray, y: np.ndarray, z: np.ndarray,
         z_norm = np.clip(z / 255.0, 0, 1)
         colors = (matplotlib.colormaps["viridis"](z_norm)[:, :3] * 255).astype(np.uint8)
     if use_binary:
-        header = ("ply\nformat binary_little_endian 1.0\n"
-                  f"element vertex {num_points}\n"
-                  "property float x\nproperty float y\nproperty float z\n"
-                  "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
-        rec = np.empty(num_points, dtype=np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"),
-                                                   ("r", "u1"), ("g", "u1"), ("b", "u1")]))
+        header = _PLY_HEADER.format(fmt="binary_little_endian", n=num_points)
+        rec = np.empty(num_points, dtype=_REC)
         rec["x"], rec["y"], rec["z"] = (np.asarray(a).astype(np.float32) for a in (x, y, z))
         rec["r"], rec["g"], rec["b"] = colors[:, 0], colors[:, 1], colors[:, 2]
         with Path(path).open("wb") as fh:
             fh.write(header.encode("ascii"))
             rec.tofile(fh)
     else:
-        header = ("ply\nformat ascii 1.0\n"
-                  f"element vertex {num_points}\n"
-                  "property float x\nproperty float y\nproperty float z\n"
-                  "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
+        header = _PLY_HEADER.format(fmt="ascii", n=num_points)
         data = np.column_stack([np.asarray(a).astype(np.float32) for a in (x, y, z)] + [colors])
         with Path(path).open("w", encoding="utf-8") as fh:
             fh.write(header)
@@ -365,13 +470,122 @@ def write_ply(path: Path, x: np.ndarray, y: np.ndarray, z: np.ndarray,
     print(f"Wrote {num_points:,} points to {Path(path).name}")
 
 
+_TORCH_NUMERIC = (torch.float16, torch.bfloat16, torch.float32, torch.float64, torch.uint8,
+                  torch.int8, torch.int16, torch.int32, torch.int64)
+_TORCH_INTS = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+
+
+def _ply_device_inputs(x, y, z, labels):
+    """(x, y, z float32, labels int32 or None) as contiguous device tensors when a GPU is there
+    and the arrays are what the kernels read, else (None, reason).  Qualifying: one-dimensional
+    arrays of one length below 2**31; real coordinates (``astype(np.float32)`` is the same
+    rounding on the device) -- the intensities float32 themselves when they colour the points,
+    as ``z / 255.0`` is a float32 division only then; integer labels that fit int32."""
+    from .core.text import gpu_visible
+
+    arrays = [x, y, z] + ([labels] if labels is not None else [])
+    for a in arrays:
+        if not isinstance(a, (np.ndarray, torch.Tensor)):
+            return None, "inputs are not arrays"
+    cuda = [a for a in arrays if isinstance(a, torch.Tensor) and a.is_cuda]
+    if not cuda and not gpu_visible():
+        return None, "no GPU"
+    n = int(x.shape[0]) if x.ndim == 1 else -1
+    if n < 0 or n >= 2**31 or any(a.ndim != 1 or int(a.shape[0]) != n for a in arrays):
+        return None, "shapes"
+    for k, a in enumerate((x, y, z)):
+        if isinstance(a, torch.Tensor):
+            ok = a.dtype in _TORCH_NUMERIC
+        else:
+            ok = a.dtype.kind in "fiu" and a.dtype.itemsize <= 8
+        if k == 2 and labels is None:
+            ok = a.dtype == (torch.float32 if isinstance(a, torch.Tensor) else np.float32)
+        if not ok:
+            return None, "dtypes"
+    if labels is not None:
+        if isinstance(labels, torch.Tensor):
+            ok, fits = labels.dtype in _TORCH_INTS, labels.dtype != torch.int64
+        else:
+            ok, fits = labels.dtype.kind in "iu", labels.dtype == np.int32
+        if not ok:
+            return None, "dtypes"
+        if n and not fits and \
+                not (int(labels.min()) >= -2**31 and int(labels.max()) < 2**31):
+            return None, "labels outside int32"
+    dev = cuda[0].device if cuda else torch.device("cuda", torch.cuda.current_device())
+    out = [to_device(a, torch.float32, dev) for a in (x, y, z)]
+    out.append(None if labels is None else to_device(labels, torch.int32, dev))
+    return out, None
+
+
+def _write_ply_device(path: Path, x, y, z, labels, use_binary: bool, signal_only: bool,
+                      size=None) -> None:
+    from .core.text import format_ply4_rows, write_text
+
+    n = int(x.numel())
+    if use_binary:
+        body = ply_records_device(x, y, z, labels, signal_only, size=size)
+        kept = body.numel() // _abi.PLY_RECORD
+    else:
+        kept = (size or ply_records_size(labels, n, True, x.device))[1] if signal_only else n
+    if kept == 0:
+        print(f"Skipping empty point cloud: {Path(path).name}")
+        return
+    if use_binary:
+        header = _PLY_HEADER.format(fmt="binary_little_endian", n=kept)
+    else:
+        rgb = ply_colors_device(z, labels)
+        if signal_only and kept < n:   # the ASCII form is off the pipeline's path: torch's index
+            m = labels >= 0
+            x, y, z, rgb = x[m], y[m], z[m], rgb[m]
+        # rows outside the "%.4f" kernel's domain (nan, inf) come from its host formatter
+        body = format_ply4_rows(x, y, z, rgb.contiguous(), as_tensor=True)
+        header = _PLY_HEADER.format(fmt="ascii", n=kept)
+    with Path(path).open("wb") as fh:
+        fh.write(header.encode("ascii"))
+        write_text(fh, body)
+    print(f"Wrote {kept:,} points to {Path(path).name}")
+
+
+def write_ply(path: Path, x, y, z, labels=None, use_binary: bool = True,
+              signal_only: bool = False, info: Optional[dict] = None, _size=None) -> None:
+    """:767-855 -- tab20 colours by label % 20 (noise grey 128), or viridis of intensity / 255
+    without labels, exactly as the reference evaluates them; numpy arrays or device tensors.
+    signal_only=True writes the points with ``labels >= 0`` only (the pipeline's
+    ``[signal_mask]`` indexing).  With a GPU and qualifying inputs (_ply_device_inputs) the
+    records -- keep rule, colours, the 15-byte layout -- are formed on the device
+    (csrc/plyrec.hip; the ASCII form takes its colours there and its rows from
+    rpt.core.text.format_ply4_rows) and only the file body crosses to the host; otherwise
+    write_ply_host runs.  ``info`` (a dict) receives ``writer`` ("device" / "host") and, for
+    "host", the ``reason``.  ``_size``: ply_records_size's result for these very labels and
+    signal_only, when the caller has it (run_pipeline's stats call)."""
+    if signal_only and labels is None:
+        raise ValueError("write_ply: signal_only needs labels")
+    dev_in, reason = _ply_device_inputs(x, y, z, labels)
+    if dev_in is not None:
+        if info is not None:
+            info["writer"] = "device"
+            info.pop("reason", None)
+        _write_ply_device(path, *dev_in, use_binary, signal_only, _size)
+        return
+    if info is not None:
+        info["writer"] = "host"
+        info["reason"] = reason
+    x, y, z, labels = (_as_host(a) for a in (x, y, z, labels))
+    if signal_only:
+        m = np.asarray(labels) >= 0
+        x, y, z, labels = x[m], y[m], z[m], labels[m]
+    write_ply_host(path, x, y, z, labels, use_binary)
+
+
 def run_pipeline(data_dir: Path, output_dir: Path, eps_space: float = DEFAULT_EPS_SPACE,
                  eps_time: float = DEFAULT_EPS_TIME, min_samples: int = DEFAULT_MIN_SAMPLES,
                  min_frames: int = DEFAULT_MIN_FRAMES, max_frames: int = 0, no_viz: bool = True,
                  skip_gif: bool = True, parallel: bool = True, low_memory: bool = False,
-                 device=None) -> Optional[dict]:
+                 device=None, info: Optional[dict] = None) -> Optional[dict]:
     """:862-1046 with the compute on the device; the same stdout lines and output files.
-    Returns the stats dict (None when no point was found)."""
+    Returns the stats dict (None when no point was found).  ``info`` (a dict) receives
+    ``ply_writers``: {file name: "device" / "host"}, which writer formed each PLY."""
     import pandas as pd
 
     print("=" * 60)
@@ -418,13 +632,17 @@ def run_pipeline(data_dir: Path, output_dir: Path, eps_space: float = DEFAULT_EP
           f"min_frames={min_frames}")
     coords = torch.stack([fr.x, fr.y], 1)
     labels_d = st_dbscan(coords, fr.t, eps_space, eps_time, min_samples, min_frames)
-    labels = labels_d.cpu().numpy()
-    noise_mask = labels == -1
-    signal_mask = ~noise_mask
-    num_clusters = len(np.unique(labels[signal_mask]))
-    stats = {"total_points": total, "noise_points": noise_mask.sum(),
-             "signal_points": signal_mask.sum(), "num_clusters": num_clusters,
-             "noise_reduction_pct": 100.0 * noise_mask.sum() / total}
+    # kept points (labels >= 0) and the largest label from the PLY writer's size pass; cluster
+    # ids are dense (numbered by their minimum core index), so there are max + 1 of them
+    n_points = int(labels_d.numel())
+    size = ply_records_size(labels_d, n_points, True, labels_d.device)
+    _, n_signal, max_label = size
+    signal_points = np.int64(n_signal)
+    noise_points = np.int64(n_points - n_signal)
+    num_clusters = max_label + 1
+    stats = {"total_points": total, "noise_points": noise_points,
+             "signal_points": signal_points, "num_clusters": num_clusters,
+             "noise_reduction_pct": 100.0 * noise_points / total}
     print("\n  Results:")
     print(f"    Total points:      {stats['total_points']:,}")
     print(f"    Noise (removed):   {stats['noise_points']:,} "
@@ -435,14 +653,18 @@ def run_pipeline(data_dir: Path, output_dir: Path, eps_space: float = DEFAULT_EP
     print("\n[5/5] Saving results...")
     out = Path(output_dir)
     out.mkdir(parents=True, exist_ok=True)
-    ax, ay, az = fr.x.cpu().numpy(), fr.y.cpu().numpy(), fr.z.cpu().numpy()
-    write_ply(out / "denoised_point_cloud.ply", ax[signal_mask], ay[signal_mask],
-              az[signal_mask], labels[signal_mask])
-    write_ply(out / "raw_point_cloud.ply", ax, ay, az)
+    writers = {}
+    for name, lab in (("denoised_point_cloud.ply", labels_d), ("raw_point_cloud.ply", None)):
+        w: dict = {}
+        write_ply(out / name, fr.x, fr.y, fr.z, lab, signal_only=lab is not None, info=w,
+                  _size=size if lab is not None else None)   # the stats call's tile offsets
+        writers[name] = w["writer"]
+    if info is not None:
+        info["ply_writers"] = writers
     pd.DataFrame([stats]).to_csv(out / "denoising_stats.csv", index=False)
     print("Saved: denoising_stats.csv")
     if num_clusters > 0:
-        cluster_table(labels_d, fr.x, fr.y, fr.z, int(labels.max()) + 1).to_csv(
+        cluster_table(labels_d, fr.x, fr.y, fr.z, max_label + 1).to_csv(
             out / "clusters.csv", index=False)
         print("Saved: clusters.csv")
     if not no_viz:
