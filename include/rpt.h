@@ -18,6 +18,9 @@
  *                                     radar_pipeline/processors/clustering.py:49-115,
  *                                     the labelling half of 4_temporal_object_tracker.py:443-506
  *   rpt_stdbscan_f64                 the same st_dbscan on float64 coordinates / float64 times
+ *   rpt_neighbour_counts             its exact neighbour counts (the quantity min_samples is tuned on)
+ *   rpt_stdbscan_sweep               st_dbscan for a list of min_samples from one grid and one count
+ *                                     pass (the min_samples axis of PointCloudWorkF/run_experiments.py)
  *   rpt_grid64_plan / _index         its grid rule on the host (no GPU)
  *   rpt_infer_time_from_colors       radar_pipeline/processors/clustering.py:17-46, 3_stdbscan...py:91-98
  *   rpt_cluster_summaries            per-frame Cluster extraction 4_temporal_object_tracker.py:508-536
@@ -196,6 +199,23 @@ int32_t rpt_stdbscan(const float* x, const float* y, const float* z, int64_t str
                      const float* times, int64_t n, double eps_space, double eps_time,
                      int32_t min_samples, int32_t* labels, rpt_stdbscan_stats* stats,
                      void* stream);
+/* counts[i] (dev int32 [n], original order) = |{ j : nbr(i, j) }|, i itself included, for the
+ * neighbour test of rpt_stdbscan; 0 for a point with a non-finite time and for every point when
+ * eps_space or eps_time is negative or NaN.  Arguments, errors and the one synchronisation (grid
+ * bounds) as rpt_stdbscan. */
+int32_t rpt_neighbour_counts(const float* x, const float* y, const float* z, int64_t stride,
+                             const float* times, int64_t n, double eps_space, double eps_time,
+                             int32_t* counts, void* stream);
+/* rpt_stdbscan for n_sets values of min_samples (host int32 [n_sets], each >= 1, 1 <= n_sets <=
+ * 64, else RPT_EINVAL) from ONE bounds pass, grid build and count pass: labels (dev int32
+ * [n_sets][n]) row k is bit-identical to rpt_stdbscan(..., min_samples[k], ...).  counts (dev
+ * int32 [n], nullable) as above.  stats (host [n_sets], nullable): n_points, n_core, n_clusters,
+ * grid per set; with timing (stats[0].timing), bounds/grid/core (the count pass) in stats[0],
+ * union/label per set.  Synchronises once more per set when stats is given (the cluster count). */
+int32_t rpt_stdbscan_sweep(const float* x, const float* y, const float* z, int64_t stride,
+                           const float* times, int64_t n, double eps_space, double eps_time,
+                           const int32_t* min_samples, int32_t n_sets, int32_t* counts,
+                           int32_t* labels, rpt_stdbscan_stats* stats, void* stream);
 /* The same contract on float64 coordinates (x, y, z: device doubles sharing `stride`; z NULL:
  * 2-D), for inputs that float32 cannot hold: decimal columns, projected coordinates with large
  * offsets, epoch times.  d2 as above on the doubles themselves.  times: n contiguous device

@@ -122,6 +122,23 @@ int32_t rpt_stdbscan(const float* x, const float* y, const float* z, int64_t str
                        stats, rpt::as_stream(stream), dim);
 }
 
+int32_t rpt_neighbour_counts(const float* x, const float* y, const float* z, int64_t stride,
+                             const float* times, int64_t n, double eps_space, double eps_time,
+                             int32_t* counts, void* stream) {
+  rpt::clear_error();
+  return rpt::neighbour_counts(x, y, z, stride, times, n, eps_space, eps_time, counts,
+                               rpt::as_stream(stream), z ? 3 : 2);
+}
+
+int32_t rpt_stdbscan_sweep(const float* x, const float* y, const float* z, int64_t stride,
+                           const float* times, int64_t n, double eps_space, double eps_time,
+                           const int32_t* min_samples, int32_t n_sets, int32_t* counts,
+                           int32_t* labels, rpt_stdbscan_stats* stats, void* stream) {
+  rpt::clear_error();
+  return rpt::stdbscan_sweep(x, y, z, stride, times, n, eps_space, eps_time, min_samples, n_sets,
+                             counts, labels, stats, rpt::as_stream(stream), z ? 3 : 2);
+}
+
 int32_t rpt_stdbscan_f64(const double* x, const double* y, const double* z, int64_t stride,
                          const void* times, int32_t time_dtype, int64_t n, double eps_space,
                          double eps_time, int32_t min_samples, int32_t* labels,

@@ -11,6 +11,17 @@ namespace rpt {
 int32_t stdbscan(const float* x, const float* y, const float* z, int64_t stride, const float* t,
                  int64_t n, double eps_space, double eps_time, int32_t min_samples,
                  int32_t* labels, rpt_stdbscan_stats* stats, hipStream_t st, int dim);
+// counts[n] (original order): the exact neighbour counts of stdbscan's neighbour test, the point
+// itself included (stdbscan_count.inc)
+int32_t neighbour_counts(const float* x, const float* y, const float* z, int64_t stride,
+                         const float* t, int64_t n, double eps_space, double eps_time,
+                         int32_t* counts, hipStream_t st, int dim);
+// stdbscan for n_sets values of min_samples (host, each >= 1) from one bounds pass, grid build and
+// count pass: labels[n_sets][n], counts[n] (nullable), stats[n_sets] (nullable)
+int32_t stdbscan_sweep(const float* x, const float* y, const float* z, int64_t stride,
+                       const float* t, int64_t n, double eps_space, double eps_time,
+                       const int32_t* min_samples, int32_t n_sets, int32_t* counts,
+                       int32_t* labels, rpt_stdbscan_stats* stats, hipStream_t st, int dim);
 // Denoise variant (PointCloudWorkF/stdbscan_denoising_pipeline.py:264-369), 2-D.
 int32_t stdbscan_denoise(const float* x, const float* y, const float* t, int64_t n,
                          double eps_space, double eps_time, int32_t min_samples,

@@ -23,6 +23,7 @@
 //   stdbscan_shared.inc  what more than one stage or the driver reads (no kernel)
 //   stdbscan_grid.inc    K4, the grid build            DbscanState::build_t
 //   stdbscan_core.inc    K5, the core flags            DbscanState::core_pass
+//   stdbscan_count.inc   the exact neighbour counts    DbscanState::count_pass, core_from_counts
 //   stdbscan_union.inc   K6, the core-core union-find  DbscanState::union_pass
 //   stdbscan_label.inc   K7/K8, ids and labels         DbscanState::cluster_ids, labels_local,
 //                                                      labels_global and the phased bodies
@@ -56,6 +57,7 @@ namespace {
 #include "stdbscan_shared.inc"
 #include "stdbscan_grid.inc"
 #include "stdbscan_core.inc"
+#include "stdbscan_count.inc"
 #include "stdbscan_union.inc"
 #include "stdbscan_label.inc"
 #include "stdbscan_frames.inc"
@@ -230,6 +232,8 @@ struct DbscanState {
     return reinterpret_cast<Pt<XY>*>(pts);
   }
   int64_t* stmp = nullptr;
+  int32_t* counts = nullptr;  // count_pass's result per sorted point, for the sweep
+  int32_t* n_core_dev = nullptr;
   Timer tm;
 
   template <int D>
@@ -240,6 +244,12 @@ struct DbscanState {
                 int64_t n_, double eps_space, double eps_time, int32_t ms, bool timing,
                 hipStream_t st);
   int32_t core_pass(hipStream_t st);
+  // the exact neighbour counts of the sorted points (stdbscan_count.inc), after build: no early
+  // exit, no min_samples.  counts_sorted: n int32 (DbscanState::counts for the sweep)
+  int32_t count_pass(int32_t* counts_sorted, hipStream_t st);
+  // core[s] = counts_sorted[s] >= m (m >= 1) as the flags of the passes that follow; the number of
+  // core points is left on the device at n_core_dev (a pre-zeroed pool word, common.h)
+  int32_t core_from_counts(const int32_t* counts_sorted, int32_t m, hipStream_t st);
   // fused: called by the fused local path (labels_local follows, the count is read back)
   int32_t union_pass(hipStream_t st, bool fused = false);
   int32_t labels_local(int32_t* labels, rpt_stdbscan_stats* stats, hipStream_t st);
@@ -389,6 +399,7 @@ int32_t DbscanState::build_t(const float* x, const float* y, const float* z, int
   bud.add<int32_t>(nt + 1);        // occ_base (slab-bucket path)
   bud.add<int32_t>((size_t)(ny * nz * nt) + 1);  // rowq (LDS-tile passes)
   bud.add<int32_t>((size_t)(ny * nz * nt) + 1);  // row counts
+  bud.add<int32_t>(n);  // counts (count_pass; kept through a min_samples sweep)
   RPT_TRY(arena.reserve(bud.bytes, st));
   (void)arena.carve_n<Bounds>(1);
   uint32_t* keys = arena.carve_n<uint32_t>(n);
@@ -429,8 +440,9 @@ int32_t DbscanState::build_t(const float* x, const float* y, const float* z, int
   int32_t* occ_base = arena.carve_n<int32_t>(nt + 1);
   rowq = arena.carve_n<int32_t>((size_t)(ny * nz * nt) + 1);
   rowcnt = arena.carve_n<int32_t>((size_t)(ny * nz * nt) + 1);
+  counts = arena.carve_n<int32_t>(n);
   rowq_ok = false;
-  if (!slab_lo || !rowcnt) {
+  if (!slab_lo || !rowcnt || !counts) {
     set_error("internal: scratch carve overflow");
     return RPT_ENOMEM;
   }
@@ -768,6 +780,33 @@ int32_t DbscanState::core_pass(hipStream_t st) {
   RPT_CHECK_LAUNCH();
   cmin_ready = cm != nullptr;
   tm.mark();
+  return RPT_OK;
+}
+
+int32_t DbscanState::count_pass(int32_t* counts_sorted, hipStream_t st) {
+  if (degenerate) return RPT_OK;  // (no grid: the callers write zeros)
+  RPT_TRY(need_float4("count_pass"));
+  with_dim(dim, [&](auto d) {
+    hipLaunchKernelGGL(k_count_cells<d.value>, dim3(wave_grid(n)), dim3(kBlock), 0, st, pts, g,
+                       occ, n_occ_dev, rec<d.value>(), occ_bits, slab_t, counts_sorted);
+  });
+  RPT_CHECK_LAUNCH();
+  tm.mark();
+  return RPT_OK;
+}
+
+int32_t DbscanState::core_from_counts(const int32_t* counts_sorted, int32_t m, hipStream_t st) {
+  if (m < 1) {  // build_t's all_mutual and labels_local's branches depend on the sign
+    set_error("core_from_counts: min_samples must be >= 1");
+    return RPT_EINVAL;
+  }
+  min_samples = g.min_samples = m;
+  cmin_ready = false;  // no core pass filled the cell minima for these flags
+  if (degenerate) return RPT_OK;
+  RPT_TRY(zero_n(st, 1, &n_core_dev));
+  hipLaunchKernelGGL(k_core_from_counts, dim3(grid_for(n, kBlock, 2048)), dim3(kBlock), 0, st,
+                     counts_sorted, n, m, core, n_core_dev);
+  RPT_CHECK_LAUNCH();
   return RPT_OK;
 }
 
@@ -1262,6 +1301,88 @@ int32_t stdbscan(const float* x, const float* y, const float* z, int64_t stride,
   RPT_TRY(S->core_pass(st));
   RPT_TRY(S->union_pass(st, stats != nullptr));  // (the guard needs labels_local's readback)
   return S->labels_local(labels, stats, st);
+}
+
+// the state's sorted counts in original order (zeros for degenerate parameters: no pair passes)
+static int32_t counts_out(DbscanState* S, int32_t* counts, hipStream_t st) {
+  if (S->degenerate) {
+    RPT_HIP(hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)S->n, st));
+    return RPT_OK;
+  }
+  hipLaunchKernelGGL(k_counts_to_orig, dim3(grid_for(S->n, kBlock, 2048)), dim3(kBlock), 0, st,
+                     S->counts, S->sorig, S->n, counts);
+  RPT_CHECK_LAUNCH();
+  return RPT_OK;
+}
+
+int32_t neighbour_counts(const float* x, const float* y, const float* z, int64_t stride,
+                         const float* t, int64_t n, double eps_space, double eps_time,
+                         int32_t* counts, hipStream_t st, int dim) {
+  if (n < 0) {
+    set_error("rpt_neighbour_counts: n < 0");
+    return RPT_EINVAL;
+  }
+  RPT_TRY(check_args(x, y, z, stride, t, n, dim));
+  if (!counts) {
+    set_error("rpt_neighbour_counts: null counts");
+    return RPT_EINVAL;
+  }
+  DbscanState* S;
+  RPT_TRY(state_for(st, &S));
+  // (min_samples 1: the grid build reads only its sign)
+  RPT_TRY(S->build(x, y, z, stride, t, n, eps_space, eps_time, 1, false, st));
+  RPT_TRY(S->count_pass(S->counts, st));
+  return counts_out(S, counts, st);
+}
+
+int32_t stdbscan_sweep(const float* x, const float* y, const float* z, int64_t stride,
+                       const float* t, int64_t n, double eps_space, double eps_time,
+                       const int32_t* min_samples, int32_t n_sets, int32_t* counts,
+                       int32_t* labels, rpt_stdbscan_stats* stats, hipStream_t st, int dim) {
+  if (n < 0) {
+    set_error("rpt_stdbscan_sweep: n < 0");
+    return RPT_EINVAL;
+  }
+  if (!min_samples || n_sets < 1 || n_sets > 64) {
+    set_error("rpt_stdbscan_sweep: n_sets must be 1 .. 64 and min_samples non-null");
+    return RPT_EINVAL;
+  }
+  for (int32_t k = 0; k < n_sets; ++k)
+    if (min_samples[k] < 1) {
+      set_error("rpt_stdbscan_sweep: min_samples[%d] = %d, every entry must be >= 1", (int)k,
+                (int)min_samples[k]);
+      return RPT_EINVAL;
+    }
+  RPT_TRY(check_args(x, y, z, stride, t, n, dim));
+  if (!labels) {
+    set_error("rpt_stdbscan_sweep: null labels");
+    return RPT_EINVAL;
+  }
+  DbscanState* S;
+  RPT_TRY(state_for(st, &S));
+  S->defer = false;  // every set's labels_local reads its cluster count back
+  const bool timing = stats && stats[0].timing;
+  RPT_TRY(S->build(x, y, z, stride, t, n, eps_space, eps_time, min_samples[0], timing, st));
+  RPT_TRY(S->count_pass(S->counts, st));  // (the timer's "core" interval)
+  if (counts) RPT_TRY(counts_out(S, counts, st));
+  for (int32_t k = 0; k < n_sets; ++k) {
+    rpt_stdbscan_stats* sk = stats ? stats + k : nullptr;
+    if (k > 0 && S->tm.on) {  // this set's union / label intervals over the first set's events
+      S->tm.k = 3;
+      S->tm.mark();
+    }
+    RPT_TRY(S->core_from_counts(S->counts, min_samples[k], st));
+    int32_t n_core = 0;
+    if (sk && !S->degenerate)  // (read by labels_local's synchronisation below)
+      RPT_HIP(hipMemcpyAsync(&n_core, S->n_core_dev, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    RPT_TRY(S->union_pass(st, sk != nullptr));  // (the guard needs labels_local's readback)
+    RPT_TRY(S->labels_local(labels + (size_t)k * (size_t)n, sk, st));
+    if (sk) {
+      sk->n_core = n_core;
+      if (k > 0) sk->ms_bounds = sk->ms_grid = sk->ms_core = 0.0;
+    }
+  }
+  return RPT_OK;
 }
 
 // Denoise variant (PointCloudWorkF/stdbscan_denoising_pipeline.py:264-369), 2-D.

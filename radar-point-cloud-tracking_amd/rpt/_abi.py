@@ -197,6 +197,11 @@ _SIGS = [
     ("rpt_stdbscan", C.c_int32,
      [vp, vp, vp, C.c_int64, vp, C.c_int64, C.c_double, C.c_double, C.c_int32, vp,
       C.POINTER(StdbscanStats), vp]),
+    ("rpt_neighbour_counts", C.c_int32,
+     [vp, vp, vp, C.c_int64, vp, C.c_int64, C.c_double, C.c_double, vp, vp]),
+    ("rpt_stdbscan_sweep", C.c_int32,
+     [vp, vp, vp, C.c_int64, vp, C.c_int64, C.c_double, C.c_double, c_i32p, C.c_int32, vp, vp,
+      C.POINTER(StdbscanStats), vp]),
     ("rpt_stdbscan_f64", C.c_int32,
      [vp, vp, vp, C.c_int64, vp, C.c_int32, C.c_int64, C.c_double, C.c_double, C.c_int32, vp,
       C.POINTER(StdbscanStats), vp]),

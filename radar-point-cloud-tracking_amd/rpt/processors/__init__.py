@@ -7,8 +7,10 @@ from .cartesian import (  # noqa: F401
 from .clustering import (  # noqa: F401
     cluster_point_cloud,
     infer_time_from_colors,
+    neighbour_counts,
     process_ply_clustering,
     st_dbscan,
+    st_dbscan_sweep,
 )
 from .point_cloud import (  # noqa: F401
     build_stacked_clouds,

@@ -222,6 +222,154 @@ def st_dbscan_soa(x: torch.Tensor, y: torch.Tensor, times: torch.Tensor, eps_spa
     return labels
 
 
+def _f32_device_inputs(coords, times, eps_time: float, what: str):
+    """(coords [n, dim] and times [n] as float32 device tensors, eps_time, n, dim, device) of an
+    input that ``_plan_inputs`` routes to the float32 kernels; the float64 route is not built for
+    ``what`` (NotImplementedError).  Shape errors as ``st_dbscan``."""
+    plan = _plan_inputs(coords, times, float(eps_time))
+    if plan.precision != "float32":
+        raise NotImplementedError(
+            f"rpt {what}: inputs that st_dbscan runs in its float64 kernel (coordinates or times "
+            "that float32 cannot hold) are not supported; use st_dbscan per min_samples")
+    c = plan.coords
+    shape = tuple(c.shape)
+    if len(shape) != 2:
+        raise ValueError(f"Expected 2D array, got {len(shape)}D array instead")
+    n, dim = shape
+    if n == 0:
+        raise ValueError(
+            f"Found array with 0 sample(s) (shape=(0, {dim})) while a minimum of 1 is required.")
+    if dim not in (2, 3):
+        raise NotImplementedError(f"rpt {what} supports 2 or 3 coordinates, got {dim}")
+    t = plan.times
+    if (t.shape[0] if is_torch(t) else len(t)) != n:
+        raise ValueError("coords and times must have the same length")
+    dev = require_gpu(c.device if is_torch(c) else None)
+    return (to_device(c, torch.float32, dev), to_device(t, torch.float32, dev), plan.eps_time, n,
+            dim, dev)
+
+
+def _counts_call(xyz, t_ptr, n, eps_space, eps_t, dev):
+    """rpt_neighbour_counts on device pointers; xyz = (x, y, z or None, stride)."""
+    counts = torch.empty(n, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        status = _abi.load().rpt_neighbour_counts(*xyz, t_ptr, n, float(eps_space), float(eps_t),
+                                                  counts.data_ptr(), stream_handle(dev))
+    _abi.check(status, "rpt_neighbour_counts")
+    return counts
+
+
+def neighbour_counts(coords, times, eps_space: float, eps_time: float):
+    """Exact neighbour counts of ``st_dbscan``'s neighbour test, the point itself included: point
+    i is core for ``min_samples = m`` exactly when ``counts[i] >= m``.  A point with a non-finite
+    time counts 0, and so does every point when an eps is negative or NaN.  int32 ``[n]``; numpy
+    in gives numpy out, tensor in a tensor on the same device."""
+    want_torch = is_torch(coords)
+    cd, td, eps_t, n, dim, dev = _f32_device_inputs(coords, times, eps_time, "neighbour_counts")
+    base = cd.data_ptr()
+    counts = _counts_call((base, base + 4, (base + 8) if dim == 3 else None, dim), td.data_ptr(),
+                          n, eps_space, eps_t, dev)
+    return counts if want_torch else counts.cpu().numpy()
+
+
+def neighbour_counts_soa(x: torch.Tensor, y: torch.Tensor, times: torch.Tensor, eps_space: float,
+                         eps_time: float, z: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``neighbour_counts`` for structure-of-arrays float32 device tensors (as st_dbscan_soa)."""
+    n = x.numel()
+    if n == 0:
+        raise ValueError("Found array with 0 sample(s) (shape=(0, 2)) while a minimum of 1 is "
+                         "required.")
+    return _counts_call((ptr(x), ptr(y), ptr(z), 1), ptr(times), n, eps_space, eps_time, x.device)
+
+
+_SWEEP_MAX_SETS = 64  # rpt_stdbscan_sweep's n_sets limit
+
+
+def _sweep_call(xyz, t_ptr, n, eps_space, eps_t, ms, dev, stats):
+    """Labels [len(ms), n] on dev: the entries >= 1 from rpt_stdbscan_sweep (64 per call), the
+    others from rpt_stdbscan; xyz = (x, y, z or None, stride) device pointers."""
+    if not ms:
+        raise ValueError("st_dbscan_sweep: min_samples must hold at least one value")
+    labels = torch.empty((len(ms), n), dtype=torch.int32, device=dev)
+    lib = _abi.load()
+    per_set = [None] * len(ms)
+    first = None  # the first swept set's stats: the shared stages' times
+    swept = [k for k, m in enumerate(ms) if m >= 1]
+    with torch.cuda.device(dev):
+        for c0 in range(0, len(swept), _SWEEP_MAX_SETS):
+            ks = swept[c0:c0 + _SWEEP_MAX_SETS]
+            # (rows of their own unless the swept sets are the consecutive rows ks[0] ..)
+            direct = ks == list(range(ks[0], ks[0] + len(ks)))
+            rows = labels[ks[0]:ks[0] + len(ks)] if direct else \
+                torch.empty((len(ks), n), dtype=torch.int32, device=dev)
+            st = (_abi.StdbscanStats * len(ks))()
+            st[0].timing = 1 if stats is not None else 0
+            msk = (_abi.C.c_int32 * len(ks))(*[ms[k] for k in ks])
+            status = lib.rpt_stdbscan_sweep(
+                *xyz, t_ptr, n, float(eps_space), float(eps_t), msk, len(ks), None,
+                rows.data_ptr(), st if stats is not None else None, stream_handle(dev))
+            _abi.check(status, "rpt_stdbscan_sweep")
+            if not direct:
+                labels[torch.as_tensor(ks, device=dev)] = rows
+            for j, k in enumerate(ks):
+                per_set[k] = st[j]
+            first = first if first is not None else st[0]
+        for k, m in enumerate(ms):
+            if m >= 1:
+                continue
+            st = _abi.StdbscanStats()
+            st.timing = 1 if stats is not None else 0
+            status = lib.rpt_stdbscan(*xyz, t_ptr, n, float(eps_space), float(eps_t), m,
+                                      labels[k].data_ptr(), st if stats is not None else None,
+                                      stream_handle(dev))
+            _abi.check(status, "rpt_stdbscan")
+            st.n_core = n  # (min_samples <= 0: every point is core, each count >= 0)
+            per_set[k] = st
+    if stats is not None:
+        head = first if first is not None else per_set[0]
+        stats.update(min_samples=list(ms), n_core=[int(s.n_core) for s in per_set],
+                     n_clusters=[int(s.n_clusters) for s in per_set],
+                     n_noise=[int(v) for v in (labels < 0).sum(dim=1).tolist()],
+                     grid_dims=tuple(head.grid_dims), grid_cells=head.grid_cells,
+                     ms_bounds=head.ms_bounds, ms_grid=head.ms_grid, ms_core=head.ms_core,
+                     ms_union=[s.ms_union for s in per_set],
+                     ms_label=[s.ms_label for s in per_set])
+    return labels
+
+
+def st_dbscan_sweep(coords, times, eps_space: float, eps_time: float, min_samples,
+                    stats: Optional[dict] = None):
+    """``st_dbscan`` for every entry of ``min_samples`` (the parameter sweep of
+    PointCloudWorkF/run_experiments.py along its min-samples axis): int32 labels
+    ``[len(min_samples), n]``, row k bit-identical to ``st_dbscan(..., min_samples[k])``.
+
+    The entries >= 1 share ONE bounds pass, grid build and exact neighbour-count pass
+    (rpt_stdbscan_sweep); entries <= 0 (every point core) take the ordinary rpt_stdbscan call.
+    ``stats`` receives ``min_samples``, ``n_core``, ``n_clusters``, ``n_noise`` as lists in the
+    order given, ``grid_dims`` and the stage times: ``ms_bounds``, ``ms_grid`` and ``ms_core`` (the
+    count pass) once, ``ms_union`` / ``ms_label`` as lists.
+    """
+    want_torch = is_torch(coords)
+    ms = [int(m) for m in min_samples]
+    cd, td, eps_t, n, dim, dev = _f32_device_inputs(coords, times, eps_time, "st_dbscan_sweep")
+    base = cd.data_ptr()
+    labels = _sweep_call((base, base + 4, (base + 8) if dim == 3 else None, dim), td.data_ptr(),
+                         n, eps_space, eps_t, ms, dev, stats)
+    return labels if want_torch else labels.cpu().numpy()
+
+
+def st_dbscan_sweep_soa(x: torch.Tensor, y: torch.Tensor, times: torch.Tensor, eps_space: float,
+                        eps_time: float, min_samples, z: Optional[torch.Tensor] = None,
+                        stats: Optional[dict] = None) -> torch.Tensor:
+    """``st_dbscan_sweep`` for structure-of-arrays float32 device tensors (as st_dbscan_soa)."""
+    n = x.numel()
+    if n == 0:
+        raise ValueError("Found array with 0 sample(s) (shape=(0, 2)) while a minimum of 1 is "
+                         "required.")
+    return _sweep_call((ptr(x), ptr(y), ptr(z), 1), ptr(times), n, eps_space, eps_time,
+                       [int(m) for m in min_samples], x.device, stats)
+
+
 def infer_time_from_colors(colors, gain_colors: Optional[Dict[int, Tuple[int, int, int]]] = None):
     """clustering.py:17-46: nearest gain tint (first minimum) -> 0, 1, 2, ... as float32."""
     if gain_colors is None:
